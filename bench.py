@@ -3,6 +3,16 @@
 Benchmark of the DANet hot path on MI355X -- contract in the task brief.
 
     python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg4|cfg4h600|cfg5|cfg5-kmeans]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step`, ...).  Everything else -- per-kernel / roofline figures, the drop-in train loop
+region (`e2e`), the parity gate against the oracle, the CPU baseline, the short `also` passes of
+other configs, the gradient-reduction schedule passes and the stand-alone all-reduce of N > 1 --
+runs only with `--full` (the `--no-*` switches below thin out a `--full` run).
+`--dump-outputs DIR` writes what the timed path returned in its LAST timed step as DIR/<name>.npy
+(float32 / float64, at most 64 MB in all: a fixed seeded sample of a larger array); the inputs
+and the initial parameters are the same in every run with the same arguments.
 
 `--gpus N` with N > 1 needs no prepared environment: when WORLD_SIZE is unset the script
 re-executes itself under `python -m torch.distributed.run --nproc-per-node N` (one rank per
@@ -408,6 +418,11 @@ def main():
     ap.add_argument('--frames', type=int)
     ap.add_argument('--layers', type=int)
     ap.add_argument('--hdim', type=int)
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline figure: roofline / per-kernel figures, e2e loop, parity gate, '
+                         'CPU baseline, `also` passes, schedule passes (off: a lean timing run)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the outputs of the last timed step as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-parity-check', action='store_true',
                     help='diagnostic sweeps only: skip the oracle comparison (parity_ok = null)')
@@ -461,16 +476,17 @@ def main():
     # configs[3] as written (4 x 600, 3-spk, truth-weighted: cfg4h600) and configs[4] (10 s inference:
     # cfg5) -- ride along as short sub-records so that they are driver-observed too; cfg 2 stays
     # the headline `value`.  Same code paths as `--config cfg4h600 / cfg5`, fewer steps, one CPU row.
-    # (diagnostic invocations -- --no-cpu-baseline / --no-parity-check, as the profiling scripts use -- skip them)
-    if (args.config == 'cfg2' and world == 1 and not use_dist and not args.no_also and not explicit_shape
-            and not args.no_cpu_baseline and not args.no_parity_check and res is not None):
+    # (diagnostic invocations -- --no-cpu-baseline / --no-parity-check, as the profiling scripts use -- skip them;
+    # --full only)
+    if (args.full and args.config == 'cfg2' and world == 1 and not use_dist and not args.no_also
+            and not explicit_shape and not args.no_cpu_baseline and not args.no_parity_check and res is not None):
         res['also'] = {}
         for name in ('cfg4h600', 'cfg5'):
             t_a = time.perf_counter()
             res['also'][name] = run_also(name, args, device)
             res['also'][name]['wall_s'] = round(time.perf_counter() - t_a, 1)
         res['also_note'] = ('short driver-visible passes of BASELINE configs[3] (as written) and configs[4]; '
-                            'full-length runs: python bench.py --config cfg4h600 | cfg5')
+                            'full-length runs: python bench.py --full --config cfg4h600 | cfg5')
     if use_dist:
         torch.distributed.destroy_process_group()
     if rank == 0:
@@ -502,6 +518,7 @@ def run_also(name, args, device):
     cfg = CONFIGS[name]
     a = copy.copy(args)
     a.config, a.steps, a.warmup, a.no_e2e, a.brief = name, 8, 2, True, True
+    a.dump_outputs = None
     a.allreduce_schedule, a.cpu_sample, a.step_times = None, None, False
     for k in ('batch', 'frames', 'layers', 'hdim'):
         setattr(a, k, cfg[k])
@@ -536,6 +553,39 @@ def max_over_ranks(dt, device, use_dist):
     return float(tt.item())
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+DUMP_KEEP_WHOLE = 4096
+
+
+def dump_outputs(out_dir, arrays):
+    '''--dump-outputs: {name: tensor / array} -> out_dir/<name>.npy, float64 kept, everything else
+    as float32.  Over DUMP_LIMIT_BYTES in all (less room for the .npy headers), every array of more
+    than DUMP_KEEP_WHOLE elements is replaced by the same fraction of its flattened elements at
+    fixed seeded positions (sorted), so that two runs with the same arguments write the same
+    sample.  -> summary for the result line'''
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    big = sum(a.nbytes for a in host.values() if a.size > DUMP_KEEP_WHOLE)
+    budget = DUMP_LIMIT_BYTES - 256 * len(host) - sum(a.nbytes for a in host.values() if a.size <= DUMP_KEEP_WHOLE)
+    frac = min(1.0, budget / max(big, 1))
+    os.makedirs(out_dir, exist_ok=True)
+    sampled = []
+    for i, name in enumerate(sorted(host)):
+        a = host[name]
+        if frac < 1.0 and a.size > DUMP_KEEP_WHOLE:
+            k = int(a.size * frac)
+            idx = np.sort(np.random.RandomState(1000 + i).choice(a.size, k, replace=False))
+            a = a.reshape(-1)[idx]
+            sampled.append(name)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    nbytes = sum(os.path.getsize(os.path.join(out_dir, n + '.npy')) for n in host)
+    log('dumped %d arrays (%d bytes) to %s%s' % (len(host), nbytes, out_dir,
+                                                 ', sampled %.4f of every array' % frac if sampled else ''))
+    return dict(arrays=len(host), bytes=nbytes, sampled_fraction=round(frac, 6) if sampled else None)
+
+
 def kernels_table(prof_all, nb):
     kern = {}
     for label, (n, ms) in prof_all.items():
@@ -544,160 +594,12 @@ def kernels_table(prof_all, nb):
     return kern
 
 
-def run_train(args, cfg, hp, device, rank, world, use_dist):
-    from danet_amd import _lib, ops
-    from danet_amd.model import Model
-    batches = make_batches(hp, rank, 4, device)
-    model = Model('bench', device=device, seed=1337, grad_schedule=args.allreduce_schedule).build()
-    log('built: %d params' % model.parameter_count())
-    barrier = make_barrier(use_dist)
-
-    # one initialisation step outside the W warmup steps: HIP code objects are loaded and the
-    # allocator pools are grown on first use (a 0.15 s one-off that must not land in the
-    # timed region when the caller asks for W = 0)
-    model.train_step(batches[0])
-    # ... and so must the runtime's one-off reaction to the host running far ahead of the GPU for
-    # the first time.  The host enqueues a step in ~1.2 ms, the GPU runs it in 3.4 ms; the first
-    # time the host gets 8-9 steps ahead (it then blocks for 6-16 ms in a launch), the recurrent
-    # kernel that is running at that moment takes 13-19 ms instead of 0.4 (tools/catch_stall.py:
-    # one `lstm_fwd` / `lstm_bwd` call, always 3-4 steps after a synchronisation, once per
-    # process, never under rocprofv3 where the host is slower).  It hit one benchmark run in five
-    # -- with K = 20 that is +1.2 ms per step.  A FIXED number (every rank must issue the same
-    # collectives) of un-synchronised untimed steps takes it here: 0 of 90 runs afterwards.
-    # Round 3: Model.train_step bounds the host's run-ahead (ops.MAX_STEPS_IN_FLIGHT steps),
-    # so that situation no longer arises and the settle phase is 8 steps (was 128); the record
-    # carries every untimed step (`init_steps`, `settle_steps`, `warmup`).
-    settle = int(os.environ.get('DANET_BENCH_SETTLE_STEPS', '8'))
-    _lib.prepare_timing()        # the timing events of the timed region exist before the untimed steps
-    for i in range(settle):
-        model.train_step(batches[i % len(batches)])
-    torch.cuda.synchronize(device)
-    for i in range(args.warmup):
-        model.train_step(batches[i % len(batches)])
-    barrier()
-    log('warmup done')
-    # timed region: HIP events only around the recurrent kernels (the roofline kernel) and
-    # only on every 4th step -- a timing event costs ~10 us of stream time on this runtime
-    # (60 pairs per step were 4 % of the step, 6 pairs per step still 3 %)
-    _lib.profile_start(only=('lstm_fwd', 'lstm_bwd'))
-    step_ev = []
-    if getattr(args, 'step_times', False):
-        step_ev.append(torch.cuda.Event(enable_timing=True)); step_ev[-1].record()
-    t0 = time.perf_counter()
-    host_ms = []
-    for i in range(args.steps):
-        _lib.profile_enable(i % 4 == 0 and os.environ.get('DANET_BENCH_EVENTS', '1') != '0')
-        th = time.perf_counter()
-        model.train_step(batches[i % len(batches)])
-        if step_ev:
-            step_ev.append(torch.cuda.Event(enable_timing=True)); step_ev[-1].record()
-            host_ms.append(1e3 * (time.perf_counter() - th))
-    _lib.profile_enable(True)
-    barrier()
-    dt = time.perf_counter() - t0
-    if step_ev:
-        log('per-step GPU ms: ' + ' '.join('%.2f' % step_ev[i].elapsed_time(step_ev[i + 1])
-                                           for i in range(len(step_ev) - 1)))
-        log('per-step host enqueue ms: ' + ' '.join('%.2f' % h for h in host_ms))
-        log('allocator: %s' % {k: v for k, v in torch.cuda.memory_stats().items()
-                               if k in ('num_alloc_retries', 'num_device_alloc', 'num_device_free',
-                                        'reserved_bytes.all.peak')})
-    prof = _lib.profile_stop()
-    prof_in_region = bool(prof)
-    # per-entry-point breakdown: a separate, untimed pass with every call instrumented
-    nb = min(10, args.steps)
-    _lib.profile_start()
-    for i in range(nb):
-        model.train_step(batches[i % len(batches)])
-    barrier()
-    prof_all = _lib.profile_stop()
-    ok = ops.lstm_status_ok()
-    log('timed region: %.3f s for %d steps; lstm status ok=%s' % (dt, args.steps, ok))
-    dt = max_over_ranks(dt, device, use_dist)
-    assert ok, 'persistent LSTM kernel reported a hand-off timeout'
-
-    # the gradient all-reduce on its own (HIP events on the current stream, which the RCCL
-    # stream is joined to): what an un-overlapped reduction adds to a step
-    allreduce_ms = None
-    if use_dist:
-        g = model._flat_grad
-        for _ in range(3):
-            torch.distributed.all_reduce(g)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            torch.distributed.all_reduce(g)
-        e1.record()
-        torch.cuda.synchronize()
-        allreduce_ms = e0.elapsed_time(e1) / 10
-        g.zero_()
-
-    mix_s_per_step = hp.BATCH_SIZE * hp.MAX_TRAIN_LEN * hp.FFT_STRIDE / hp.SMPRATE
-    value = world * mix_s_per_step * args.steps / dt
-    # second timed region (not `value`): the same K steps through the drop-in train loop with
-    # batches that start in HOST memory (every rank runs it: the steps contain the all-reduce)
-    e2e = None
-    if not args.no_e2e:
-        dt_e, nbytes, rep_e, n_unt, n_tim = run_e2e(args, hp, model, device, rank, use_dist, barrier)
-        dt_s, _, _, _, _ = run_e2e(args, hp, model, device, rank, use_dist, barrier, sync_feed=True)
-        assert ops.lstm_status_ok()
-        e2e = dict(loop='cli.train_epoch (main.py:413-436): host numpy batches [B*C, T+32, F] -> crop '
-                        '-> pinned staging -> async upload one batch ahead (side stream) -> train_step; metrics '
-                        'read once per epoch',
-                   ms_per_step=round(1e3 * dt_e / args.steps, 3),
-                   value=round(world * mix_s_per_step * args.steps / dt_e, 2),
-                   frac_of_resident=round(dt / dt_e, 4), untimed_steps=n_unt, timed_steps=n_tim,
-                   host_batch_bytes=int(nbytes),
-                   uploaded_bytes_per_step=int(nbytes * hp.MAX_TRAIN_LEN // (hp.MAX_TRAIN_LEN + 32)),
-                   sync_feed_ms_per_step=round(1e3 * dt_s / args.steps, 3),
-                   sync_feed_note='the reference\'s literal loop: blocking upload from pageable '
-                                  'memory + float() of loss / SNR every step',
-                   epoch_mean_loss=rep_e['loss'])
-        log('e2e train loop: %.3f ms/step (resident %.3f, sync feed %.3f)'
-            % (e2e['ms_per_step'], 1e3 * dt / args.steps, e2e['sync_feed_ms_per_step']))
-    # N > 1: ONE run settles the reduction schedule.  `value` above is the schedule the model was
-    # built with (default 'auto': '0' = one all-reduce after backward, or 'tail' if the model's own measurement of the
-    # collective against its step says so -- `grad_allreduce_decision`); the same K steps are now timed with
-    # the other schedules and with NO reduction at all (what the step costs without communication),
-    # every rank taking part in every pass.  exposed = schedule - no_reduction.
-    sched_ms = None
-    if use_dist and world > 1 and not args.no_schedules:
-        from danet_amd import dist as D
-
-        def time_schedule(sched, reduce=True):
-            m = Model('bench_' + sched, device=device, seed=1337, grad_schedule=sched).build()
-            orig = D.allreduce_grads_
-            if not reduce:
-                D.allreduce_grads_ = lambda g: 1.0 / D.world_size()
-            try:
-                for i in range(4 + max(args.warmup, 2)):
-                    m.train_step(batches[i % len(batches)])
-                barrier()
-                t0 = time.perf_counter()
-                for i in range(args.steps):
-                    m.train_step(batches[i % len(batches)])
-                barrier()
-                d = max_over_ranks(time.perf_counter() - t0, device, use_dist)
-            finally:
-                D.allreduce_grads_ = orig
-            assert ops.lstm_status_ok()
-            return round(1e3 * d / args.steps, 3)
-        sched_ms = {model.grad_schedule: round(1e3 * dt / args.steps, 3)}
-        for sc in ('0', 'tail', '1'):
-            if sc not in sched_ms:
-                sched_ms[sc] = time_schedule(sc)
-        none = time_schedule('0', reduce=False)
-        sched_ms = dict(ms_per_step=sched_ms, no_reduction_ms_per_step=none,
-                        exposed_comm_ms={k: round(v - none, 3) for k, v in sched_ms.items()},
-                        note="'0' one all-reduce after backward | 'tail' everything outside the bottom encoder "
-                             "layer reduced under that layer's weight-gradient GEMMs | '1' per-layer buckets; "
-                             "no_reduction = the same steps with the collective skipped (replicas drift: timing only)")
-    if rank != 0:
-        return None
-
+def train_roofline(args, hp, prof, prof_all, prof_in_region, nb):
+    '''--full: the recurrent kernels' (and the GEMMs') achieved rate against the matrix-core peak,
+    from the events of the timed region (prof) and of the instrumented pass (prof_all)'''
+    from danet_amd import _lib
     B, T, H, L = hp.BATCH_SIZE, hp.MAX_TRAIN_LEN, hp.LSTM_HDIM, hp.NUM_LSTM_LAYERS
-    C, E, F = hp.MAX_N_SIGNAL, hp.EMBED_SIZE, hp.FFT_SIZE // 2 + 1
+    E, F = hp.EMBED_SIZE, hp.FFT_SIZE // 2 + 1
     # algorithmic flops per launch (DESIGN.md): the recurrent half of one BiLSTM layer, plus --
     # where the fused kernels run (csrc/lstm.hip) -- the input projection (forward) / the
     # weight gradients (BPTT) that the same launch computes; averaged over the L layers
@@ -764,6 +666,177 @@ def run_train(args, cfg, hp, device, rank, world, use_dist):
                                          'and fp32-accurate results throughout: the x6 kernels form '
                                          'each product from six bf16 piece products '
                                          '(csrc/gemm_x6.hip)' % (gn // nb))
+    return roofline
+
+
+def run_train(args, cfg, hp, device, rank, world, use_dist):
+    from danet_amd import _lib, ops
+    from danet_amd.model import Model
+    batches = make_batches(hp, rank, 4, device)
+    model = Model('bench', device=device, seed=1337, grad_schedule=args.allreduce_schedule).build()
+    log('built: %d params' % model.parameter_count())
+    barrier = make_barrier(use_dist)
+
+    # one initialisation step outside the W warmup steps: HIP code objects are loaded and the
+    # allocator pools are grown on first use (a 0.15 s one-off that must not land in the
+    # timed region when the caller asks for W = 0)
+    model.train_step(batches[0])
+    # ... and so must the runtime's one-off reaction to the host running far ahead of the GPU for
+    # the first time.  The host enqueues a step in ~1.2 ms, the GPU runs it in 3.4 ms; the first
+    # time the host gets 8-9 steps ahead (it then blocks for 6-16 ms in a launch), the recurrent
+    # kernel that is running at that moment takes 13-19 ms instead of 0.4 (tools/catch_stall.py:
+    # one `lstm_fwd` / `lstm_bwd` call, always 3-4 steps after a synchronisation, once per
+    # process, never under rocprofv3 where the host is slower).  It hit one benchmark run in five
+    # -- with K = 20 that is +1.2 ms per step.  A FIXED number (every rank must issue the same
+    # collectives) of un-synchronised untimed steps takes it here: 0 of 90 runs afterwards.
+    # Round 3: Model.train_step bounds the host's run-ahead (ops.MAX_STEPS_IN_FLIGHT steps),
+    # so that situation no longer arises and the settle phase is 8 steps (was 128); the record
+    # carries every untimed step (`init_steps`, `settle_steps`, `warmup`).
+    settle = int(os.environ.get('DANET_BENCH_SETTLE_STEPS', '8'))
+    if args.full:
+        _lib.prepare_timing()    # the timing events of the timed region exist before the untimed steps
+    for i in range(settle):
+        model.train_step(batches[i % len(batches)])
+    torch.cuda.synchronize(device)
+    for i in range(args.warmup):
+        model.train_step(batches[i % len(batches)])
+    barrier()
+    log('warmup done')
+    # timed region (--full): HIP events only around the recurrent kernels (the roofline kernel) and
+    # only on every 4th step -- a timing event costs ~10 us of stream time on this runtime
+    # (60 pairs per step were 4 % of the step, 6 pairs per step still 3 %); a plain run records none
+    if args.full:
+        _lib.profile_start(only=('lstm_fwd', 'lstm_bwd'))
+    step_ev = []
+    if getattr(args, 'step_times', False):
+        step_ev.append(torch.cuda.Event(enable_timing=True)); step_ev[-1].record()
+    t0 = time.perf_counter()
+    host_ms = []
+    for i in range(args.steps):
+        if args.full:
+            _lib.profile_enable(i % 4 == 0 and os.environ.get('DANET_BENCH_EVENTS', '1') != '0')
+        th = time.perf_counter()
+        last = model.train_step(batches[i % len(batches)])
+        if step_ev:
+            step_ev.append(torch.cuda.Event(enable_timing=True)); step_ev[-1].record()
+            host_ms.append(1e3 * (time.perf_counter() - th))
+    if args.full:
+        _lib.profile_enable(True)
+    barrier()
+    dt = time.perf_counter() - t0
+    if step_ev:
+        log('per-step GPU ms: ' + ' '.join('%.2f' % step_ev[i].elapsed_time(step_ev[i + 1])
+                                           for i in range(len(step_ev) - 1)))
+        log('per-step host enqueue ms: ' + ' '.join('%.2f' % h for h in host_ms))
+        log('allocator: %s' % {k: v for k, v in torch.cuda.memory_stats().items()
+                               if k in ('num_alloc_retries', 'num_device_alloc', 'num_device_free',
+                                        'reserved_bytes.all.peak')})
+    ok = ops.lstm_status_ok()
+    # what a caller of train_step receives from the last timed step: loss, SNR and the parameters
+    # that step's optimizer update left (before any further step runs; not after a hand-off timeout)
+    dumped = None
+    if ok and args.dump_outputs and rank == 0:
+        outs = dict(loss=last['loss'], SNR=last['SNR'])
+        outs.update(('param.' + k.replace('/', '.'), v) for k, v in model.vars.items())
+        dumped = dump_outputs(args.dump_outputs, outs)
+    nb = min(10, args.steps)
+    prof, prof_all = {}, {}
+    if args.full:
+        prof = _lib.profile_stop()
+        # per-entry-point breakdown: a separate, untimed pass with every call instrumented
+        _lib.profile_start()
+        for i in range(nb):
+            model.train_step(batches[i % len(batches)])
+        barrier()
+        prof_all = _lib.profile_stop()
+        ok = ops.lstm_status_ok() and ok
+    prof_in_region = bool(prof)
+    log('timed region: %.3f s for %d steps; lstm status ok=%s' % (dt, args.steps, ok))
+    dt = max_over_ranks(dt, device, use_dist)
+    assert ok, 'persistent LSTM kernel reported a hand-off timeout'
+
+    # the gradient all-reduce on its own (HIP events on the current stream, which the RCCL
+    # stream is joined to): what an un-overlapped reduction adds to a step
+    allreduce_ms = None
+    if use_dist and args.full:
+        g = model._flat_grad
+        for _ in range(3):
+            torch.distributed.all_reduce(g)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(10):
+            torch.distributed.all_reduce(g)
+        e1.record()
+        torch.cuda.synchronize()
+        allreduce_ms = e0.elapsed_time(e1) / 10
+        g.zero_()
+
+    mix_s_per_step = hp.BATCH_SIZE * hp.MAX_TRAIN_LEN * hp.FFT_STRIDE / hp.SMPRATE
+    value = world * mix_s_per_step * args.steps / dt
+    # second timed region (not `value`): the same K steps through the drop-in train loop with
+    # batches that start in HOST memory (every rank runs it: the steps contain the all-reduce)
+    e2e = None
+    if args.full and not args.no_e2e:
+        dt_e, nbytes, rep_e, n_unt, n_tim = run_e2e(args, hp, model, device, rank, use_dist, barrier)
+        dt_s, _, _, _, _ = run_e2e(args, hp, model, device, rank, use_dist, barrier, sync_feed=True)
+        assert ops.lstm_status_ok()
+        e2e = dict(loop='cli.train_epoch (main.py:413-436): host numpy batches [B*C, T+32, F] -> crop '
+                        '-> pinned staging -> async upload one batch ahead (side stream) -> train_step; metrics '
+                        'read once per epoch',
+                   ms_per_step=round(1e3 * dt_e / args.steps, 3),
+                   value=round(world * mix_s_per_step * args.steps / dt_e, 2),
+                   frac_of_resident=round(dt / dt_e, 4), untimed_steps=n_unt, timed_steps=n_tim,
+                   host_batch_bytes=int(nbytes),
+                   uploaded_bytes_per_step=int(nbytes * hp.MAX_TRAIN_LEN // (hp.MAX_TRAIN_LEN + 32)),
+                   sync_feed_ms_per_step=round(1e3 * dt_s / args.steps, 3),
+                   sync_feed_note='the reference\'s literal loop: blocking upload from pageable '
+                                  'memory + float() of loss / SNR every step',
+                   epoch_mean_loss=rep_e['loss'])
+        log('e2e train loop: %.3f ms/step (resident %.3f, sync feed %.3f)'
+            % (e2e['ms_per_step'], 1e3 * dt / args.steps, e2e['sync_feed_ms_per_step']))
+    # N > 1: ONE run settles the reduction schedule.  `value` above is the schedule the model was
+    # built with (default 'auto': '0' = one all-reduce after backward, or 'tail' if the model's own measurement of the
+    # collective against its step says so -- `grad_allreduce_decision`); the same K steps are now timed with
+    # the other schedules and with NO reduction at all (what the step costs without communication),
+    # every rank taking part in every pass.  exposed = schedule - no_reduction.
+    sched_ms = None
+    if args.full and use_dist and world > 1 and not args.no_schedules:
+        from danet_amd import dist as D
+
+        def time_schedule(sched, reduce=True):
+            m = Model('bench_' + sched, device=device, seed=1337, grad_schedule=sched).build()
+            orig = D.allreduce_grads_
+            if not reduce:
+                D.allreduce_grads_ = lambda g: 1.0 / D.world_size()
+            try:
+                for i in range(4 + max(args.warmup, 2)):
+                    m.train_step(batches[i % len(batches)])
+                barrier()
+                t0 = time.perf_counter()
+                for i in range(args.steps):
+                    m.train_step(batches[i % len(batches)])
+                barrier()
+                d = max_over_ranks(time.perf_counter() - t0, device, use_dist)
+            finally:
+                D.allreduce_grads_ = orig
+            assert ops.lstm_status_ok()
+            return round(1e3 * d / args.steps, 3)
+        sched_ms = {model.grad_schedule: round(1e3 * dt / args.steps, 3)}
+        for sc in ('0', 'tail', '1'):
+            if sc not in sched_ms:
+                sched_ms[sc] = time_schedule(sc)
+        none = time_schedule('0', reduce=False)
+        sched_ms = dict(ms_per_step=sched_ms, no_reduction_ms_per_step=none,
+                        exposed_comm_ms={k: round(v - none, 3) for k, v in sched_ms.items()},
+                        note="'0' one all-reduce after backward | 'tail' everything outside the bottom encoder "
+                             "layer reduced under that layer's weight-gradient GEMMs | '1' per-layer buckets; "
+                             "no_reduction = the same steps with the collective skipped (replicas drift: timing only)")
+    if rank != 0:
+        return None
+
+    B, T, H, L = hp.BATCH_SIZE, hp.MAX_TRAIN_LEN, hp.LSTM_HDIM, hp.NUM_LSTM_LAYERS
+    C, E, F = hp.MAX_N_SIGNAL, hp.EMBED_SIZE, hp.FFT_SIZE // 2 + 1
     est = hp.TRAIN_ESTIMATOR_METHOD
     res = dict(metric='mixture-seconds/s (train step)', value=round(value, 2),
                unit='mixture-seconds/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
@@ -783,9 +856,15 @@ def run_train(args, cfg, hp, device, rank, world, use_dist):
                init_steps=1, settle_steps=settle,
                untimed_steps_total=1 + settle + args.warmup,
                max_steps_in_flight=ops.MAX_STEPS_IN_FLIGHT,
-               rccl_ranks=(torch.distributed.get_world_size() if use_dist else 0),
-               allreduce_ms_standalone=(round(allreduce_ms, 4) if allreduce_ms is not None else None),
-               roofline=roofline, kernels=kernels_table(prof_all, nb), host=host_info())
+               rccl_ranks=(torch.distributed.get_world_size() if use_dist else 0), host=host_info())
+    if dumped is not None:
+        res['dumped_outputs'] = dumped
+    if not args.full:
+        res['parity_ok'] = None
+        return res
+    res.update(allreduce_ms_standalone=(round(allreduce_ms, 4) if allreduce_ms is not None else None),
+               roofline=train_roofline(args, hp, prof, prof_all, prof_in_region, nb),
+               kernels=kernels_table(prof_all, nb))
     if e2e is not None:
         res['e2e'] = e2e
     if world == 1:
@@ -916,35 +995,63 @@ def run_infer(args, cfg, hp, device, rank, world, use_dist):
     y = step(waves[0])
     assert tuple(y.shape) == (hp.MAX_N_SIGNAL, T * S), y.shape
     settle = int(os.environ.get('DANET_BENCH_SETTLE_STEPS', '8'))                  # see run_train
-    _lib.prepare_timing()
+    if args.full:
+        _lib.prepare_timing()
     for i in range(settle):
         step(waves[i % len(waves)])
     torch.cuda.synchronize(device)
     for i in range(args.warmup):
         step(waves[i % len(waves)])
     barrier()
-    _lib.profile_start(only=('lstm_fwd',))
+    if args.full:
+        _lib.profile_start(only=('lstm_fwd',))
     t0 = time.perf_counter()
     for i in range(args.steps):
-        _lib.profile_enable(i % 4 == 0)
-        step(waves[i % len(waves)])
-    _lib.profile_enable(True)
+        if args.full:
+            _lib.profile_enable(i % 4 == 0)
+        y = step(waves[i % len(waves)])
+    if args.full:
+        _lib.profile_enable(True)
     barrier()
     dt = time.perf_counter() - t0
-    prof = _lib.profile_stop()
-    nb = min(10, args.steps)
-    _lib.profile_start()
-    for i in range(nb):
-        step(waves[i % len(waves)])
-    barrier()
-    prof_all = _lib.profile_stop()
     ok = ops.lstm_status_ok()
+    dumped = None
+    if ok and args.dump_outputs and rank == 0:
+        # what the demo path hands back for the last timed utterance: the separated waveforms
+        dumped = dump_outputs(args.dump_outputs, dict(separated_waves=y))
+    nb = min(10, args.steps)
+    prof, prof_all = {}, {}
+    if args.full:
+        prof = _lib.profile_stop()
+        _lib.profile_start()
+        for i in range(nb):
+            step(waves[i % len(waves)])
+        barrier()
+        prof_all = _lib.profile_stop()
+        ok = ops.lstm_status_ok() and ok
     dt = max_over_ranks(dt, device, use_dist)
     assert ok, 'persistent LSTM kernel reported a hand-off timeout'
     if rank != 0:
         return None
     H, L, F, E = hp.LSTM_HDIM, hp.NUM_LSTM_LAYERS, hp.FFT_SIZE // 2 + 1, hp.EMBED_SIZE
     mix_s = T * S / hp.SMPRATE
+    res = dict(metric='mixture-seconds/s (inference, demo path)', value=round(world * mix_s * args.steps / dt, 2),
+               unit='mixture-seconds/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
+               ms_per_step=round(1e3 * dt / args.steps, 3), higher_is_better=True,
+               scaling='weak', vs_baseline=None, dtype='f32', data='synthetic', dtype_note=DTYPE_NOTE,
+               config=dict(workload='%s: synthetic %d Hz %d-spk utterance of %.1f s, FFT %d/%d (%d bins), '
+                                    'T=%d, %dx%d BiLSTM, E=%d, %s estimator, B=1: stft -> infer -> istft'
+                                    % (args.config, hp.SMPRATE, hp.MAX_N_SIGNAL, mix_s, N, S, F, T, L, H,
+                                       E, hp.INFER_ESTIMATOR_METHOD),
+                           global_batch=world, parallelism='replicas%d' % world),
+               init_steps=1, settle_steps=settle, untimed_steps_total=1 + settle + args.warmup,
+               max_steps_in_flight=ops.MAX_STEPS_IN_FLIGHT,
+               rccl_ranks=(torch.distributed.get_world_size() if use_dist else 0), host=host_info())
+    if dumped is not None:
+        res['dumped_outputs'] = dumped
+    if not args.full:
+        res['parity_ok'] = None
+        return res
     n, ms = prof['lstm_fwd']
     per_launch_s = ms / n * 1e-3
     # B = 1 recurrence: the per-step product is a GEMV.  Algorithmic HBM bytes of one launch
@@ -966,19 +1073,7 @@ def run_infer(args, cfg, hp, device, rank, world, use_dist):
                     note='B=1: T dependent GEMV steps per launch, latency-bound; weights stationary, '
                          'so the HBM fraction of the algorithmic bytes is tiny by design '
                          '(DESIGN.md 3.1); us_per_timestep is the meaningful figure')
-    res = dict(metric='mixture-seconds/s (inference, demo path)', value=round(world * mix_s * args.steps / dt, 2),
-                unit='mixture-seconds/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
-                ms_per_step=round(1e3 * dt / args.steps, 3), higher_is_better=True,
-                scaling='weak', vs_baseline=None, dtype='f32', data='synthetic', dtype_note=DTYPE_NOTE,
-                config=dict(workload='%s: synthetic %d Hz %d-spk utterance of %.1f s, FFT %d/%d (%d bins), '
-                                     'T=%d, %dx%d BiLSTM, E=%d, %s estimator, B=1: stft -> infer -> istft'
-                                     % (args.config, hp.SMPRATE, hp.MAX_N_SIGNAL, mix_s, N, S, F, T, L, H,
-                                        E, hp.INFER_ESTIMATOR_METHOD),
-                            global_batch=world, parallelism='replicas%d' % world),
-                init_steps=1, settle_steps=settle, untimed_steps_total=1 + settle + args.warmup,
-                max_steps_in_flight=ops.MAX_STEPS_IN_FLIGHT,
-                rccl_ranks=(torch.distributed.get_world_size() if use_dist else 0),
-                roofline=roofline, kernels=kernels_table(prof_all, nb), host=host_info())
+    res.update(roofline=roofline, kernels=kernels_table(prof_all, nb))
     if world == 1:
         torch.set_num_threads(min(os.cpu_count() or 1, 16))
         if args.no_parity_check:

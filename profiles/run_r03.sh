@@ -10,9 +10,9 @@ OUT=$ROOT/gpurun_out/r03
 mkdir -p "$OUT"
 cd "$ROOT"
 for c in cfg2 cfg4 cfg4h600 cfg5 cfg5-kmeans; do
-  python bench.py --config $c --steps 20 --warmup 5 2> "$OUT/${TAG}_bench_$c.err" | tail -1 > "$OUT/${TAG}_bench_$c.json"
+  python bench.py --full --config $c --steps 20 --warmup 5 2> "$OUT/${TAG}_bench_$c.err" | tail -1 > "$OUT/${TAG}_bench_$c.json"
 done
-DANET_FORCE_DIST=1 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_cfg2_rccl1.json"
+DANET_FORCE_DIST=1 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_cfg2_rccl1.json"
 for c in cfg2 cfg4 cfg4h600 cfg5; do
   bash profiles/run_rocprof.sh ${TAG}_$c --config $c > "$OUT/${TAG}_rocprof_$c.log" 2>&1
   cp gpurun_out/prof_${TAG}_$c/kernel_stats.csv "$OUT/${TAG}_kernel_stats_$c.csv" 2>/dev/null

@@ -10,9 +10,9 @@ OUT=$ROOT/gpurun_out/r04
 mkdir -p "$OUT"
 cd "$ROOT"
 for c in cfg2 cfg4 cfg4h600 cfg5 cfg5-kmeans; do
-  python bench.py --config $c --steps 20 --warmup 5 2> "$OUT/${TAG}_bench_$c.err" | tail -1 > "$OUT/${TAG}_bench_$c.json"
+  python bench.py --full --config $c --steps 20 --warmup 5 2> "$OUT/${TAG}_bench_$c.err" | tail -1 > "$OUT/${TAG}_bench_$c.json"
 done
-DANET_FORCE_DIST=1 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_cfg2_rccl1.json"
+DANET_FORCE_DIST=1 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_cfg2_rccl1.json"
 for c in cfg2 cfg4 cfg4h600 cfg5; do
   bash profiles/run_rocprof.sh ${TAG}_$c --config $c > "$OUT/${TAG}_rocprof_$c.log" 2>&1
   cp gpurun_out/prof_${TAG}_$c/kernel_stats.csv "$OUT/${TAG}_kernel_stats_$c.csv" 2>/dev/null
@@ -30,7 +30,7 @@ python tools/bench_gemm.py > "$OUT/${TAG}_gemm_shapes.txt" 2>&1
 python tools/bench_gemm_x6_nt.py > "$OUT/${TAG}_gemm_x6_nt.txt" 2>&1
 python tools/bench_gemm_x6_tn.py > "$OUT/${TAG}_gemm_x6_tn.txt" 2>&1
 python tools/bptt_neighbour_probe.py > "$OUT/${TAG}_bptt_neighbour.txt" 2>&1
-DANET_GEMM_X6=0 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_cfg2_exact_fp32_gemms.json"
+DANET_GEMM_X6=0 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_cfg2_exact_fp32_gemms.json"
 python tools/lstm_modes.py > "$OUT/${TAG}_lstm_bwd_modes.txt" 2>&1
 python tools/feed_probe.py 100 > "$OUT/${TAG}_feed_probe.txt" 2>&1
 python tools/feed_trace.py ahead 100 3 > "$OUT/${TAG}_feed_trace.txt" 2>&1

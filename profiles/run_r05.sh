@@ -9,12 +9,12 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/r05
 mkdir -p "$OUT"
 cd "$ROOT"
-# the driver's command first (default: cfg 2 + the short cfg4h600 / cfg5 sub-records), then every config at full length
-python bench.py 2> "$OUT/${TAG}_bench_default.err" | tail -1 > "$OUT/${TAG}_bench_default.json"
+# the default line's full record first (cfg 2 + the short cfg4h600 / cfg5 sub-records), then every config at full length
+python bench.py --full 2> "$OUT/${TAG}_bench_default.err" | tail -1 > "$OUT/${TAG}_bench_default.json"
 for c in cfg2 cfg4 cfg4h600 cfg5 cfg5-kmeans; do
-  python bench.py --config $c --steps 20 --warmup 5 --no-also 2> "$OUT/${TAG}_bench_$c.err" | tail -1 > "$OUT/${TAG}_bench_$c.json"
+  python bench.py --full --config $c --steps 20 --warmup 5 --no-also 2> "$OUT/${TAG}_bench_$c.err" | tail -1 > "$OUT/${TAG}_bench_$c.json"
 done
-DANET_FORCE_DIST=1 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-also 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_cfg2_rccl1.json"
+DANET_FORCE_DIST=1 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-also 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_cfg2_rccl1.json"
 for c in cfg2 cfg4 cfg4h600 cfg5; do
   bash profiles/run_rocprof.sh ${TAG}_$c --config $c > "$OUT/${TAG}_rocprof_$c.log" 2>&1
   cp gpurun_out/prof_${TAG}_$c/kernel_stats.csv "$OUT/${TAG}_kernel_stats_$c.csv" 2>/dev/null
@@ -34,7 +34,7 @@ python tools/bench_gemm_x6_tn.py > "$OUT/${TAG}_gemm_x6_tn.txt" 2>&1
 python tools/bptt_neighbour_probe.py > "$OUT/${TAG}_bptt_neighbour.txt" 2>&1
 # every product on the exact-fp32 matrix instructions (x6 off, hoisted input half + unfused forward): the same
 # step count before the mask check as the default line (e2e on)
-DANET_GEMM_X6=0 DANET_LSTM_FWD_FUSED=0 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-also 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_cfg2_exact_fp32.json"
+DANET_GEMM_X6=0 DANET_LSTM_FWD_FUSED=0 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-also 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_cfg2_exact_fp32.json"
 DANET_LSTM_FWD_FUSED=1 python tools/trace_lstm.py > "$OUT/${TAG}_lstm_phase_trace.txt" 2>&1
 python tools/lstm_modes.py > "$OUT/${TAG}_lstm_bwd_modes.txt" 2>&1
 python tools/feed_probe.py 100 > "$OUT/${TAG}_feed_probe.txt" 2>&1

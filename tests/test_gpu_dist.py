@@ -93,7 +93,7 @@ def test_bench_spawn_path_one_rank():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4',
-                          '--warmup', '1', '--no-cpu-baseline'],
+                          '--warmup', '1', '--no-cpu-baseline', '--full'],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     res = json.loads(out.stdout.strip().splitlines()[-1])
@@ -101,6 +101,72 @@ def test_bench_spawn_path_one_rank():
     assert res['allreduce_ms_standalone'] is not None
     assert res['config']['workload'].startswith('cfg2')
     assert res['roofline']['events_in_timed_region'] is True
+
+
+def test_bench_plain_run_dumps_last_step(hp, tmp_path):
+    '''a plain `python bench.py` (no --full) prints the headline fields only, and --dump-outputs
+    writes the loss, SNR and updated parameters of the LAST timed step: two runs with the same
+    arguments write the same arrays, and they are those of an in-process replay of the run's step
+    sequence after its last step -- not the initial parameters, not those one step earlier'''
+    import types
+    from danet_amd.model import Model
+    sys.path.insert(0, ROOT)
+    import bench
+    env = dict(os.environ)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'DANET_FORCE_DIST', 'DANET_BENCH_SETTLE_STEPS'):
+        env.pop(k, None)
+    steps, warmup, settle = 3, 1, 8
+    dumps = []
+    for run in ('a', 'b'):
+        out_dir = tmp_path / run
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps),
+                              '--warmup', str(warmup), '--batch', '8', '--frames', '32',
+                              '--dump-outputs', str(out_dir)],
+                             capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+        res = json.loads(out.stdout.strip().splitlines()[-1])
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert k in res, k
+        assert res['steps'] == steps and res['untimed_steps_total'] == 1 + settle + warmup
+        assert res['value'] > 0 and res['dtype'] == 'f32'
+        per_step = 8 * 32 * 64 / 8000.0
+        assert abs(res['value'] - per_step / (res['ms_per_step'] * 1e-3)) < 1e-2 * res['value']
+        for k in ('roofline', 'kernels', 'e2e', 'cpu_baseline', 'parity', 'also', 'schedules'):
+            assert k not in res, k
+        assert res['parity_ok'] is None
+        files = sorted(os.listdir(out_dir))
+        assert 'loss.npy' in files and 'SNR.npy' in files and res['dumped_outputs']['arrays'] == len(files)
+        assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 * 1000 * 1000
+        d = {f[:-4]: np.load(out_dir / f) for f in files}
+        for f, a in d.items():
+            assert a.dtype == np.float32 and np.isfinite(a).all(), f
+        dumps.append(d)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    # replay: bench.py's inputs, model and step sequence (1 init + settle + warmup + timed steps)
+    bench.setup_hparams(types.SimpleNamespace(batch=8, frames=32, layers=3, hdim=300), bench.CONFIGS['cfg2'])
+    dev = torch.device('cuda', 0)
+    batches = bench.make_batches(hp, 0, 4, dev)
+    model = Model('bench', device=dev, seed=1337).build()
+
+    def snap():
+        return {'param.' + k.replace('/', '.'): v.detach().cpu().numpy().copy() for k, v in model.vars.items()}
+    init = snap()
+    seq = [0] + [i % 4 for i in range(settle)] + [i % 4 for i in range(warmup)] + [i % 4 for i in range(steps)]
+    for i in seq[:-1]:
+        model.train_step(batches[i])
+    prev = snap()
+    last = model.train_step(batches[seq[-1]])
+    final = snap()
+    got = dumps[0]
+    assert set(final) == {k for k in got if k.startswith('param.')}
+
+    def max_rel(ref):
+        return max(float(np.abs(got[k] - ref[k]).max() / max(np.abs(ref[k]).max(), 1e-30)) for k in ref)
+    assert max_rel(final) <= 1e-5, max_rel(final)
+    assert max_rel(prev) >= 1e-4 and max_rel(init) >= 1e-4, (max_rel(prev), max_rel(init))
+    assert abs(got['loss'].item() - last['loss'].item()) <= 1e-5 * abs(last['loss'].item())
 
 
 # ------------------------------------------------ data parallel, 2 ranks, the HIP path (one GPU)
@@ -240,7 +306,7 @@ def test_bench_two_ranks_functional(tmp_path):
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'DANET_FORCE_DIST'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4',
-                          '--warmup', '1', '--no-cpu-baseline', '--batch', '8', '--frames', '32'],
+                          '--warmup', '1', '--no-cpu-baseline', '--batch', '8', '--frames', '32', '--full'],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     res = json.loads(out.stdout.strip().splitlines()[-1])

@@ -277,6 +277,32 @@ def test_bench_cli_surface():
         os.environ.update(env)
 
 
+def test_bench_dump_outputs_dtype_and_cap(tmp_path, monkeypatch):
+    '''bench.dump_outputs: float64 stays float64, everything else is written as float32; over the
+    cap every large array is cut to the same fixed seeded sample, identical from call to call'''
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.RandomState(0)
+    arrays = dict(a=rng.rand(300, 200), b=torch.tensor(rng.rand(5000), dtype=torch.float32),
+                  c=np.int32(7))
+    s = bench.dump_outputs(str(tmp_path / 'full'), arrays)
+    assert s['arrays'] == 3 and s['sampled_fraction'] is None
+    a, b, c = (np.load(tmp_path / 'full' / (n + '.npy')) for n in 'abc')
+    assert a.dtype == np.float64 and np.array_equal(a, arrays['a'])
+    assert b.dtype == np.float32 and np.array_equal(b, arrays['b'].numpy())
+    assert c.dtype == np.float32 and c == 7
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 100000)
+    monkeypatch.setattr(bench, 'DUMP_KEEP_WHOLE', 10)
+    s1 = bench.dump_outputs(str(tmp_path / 's1'), arrays)
+    s2 = bench.dump_outputs(str(tmp_path / 's2'), arrays)
+    assert 0 < s1['sampled_fraction'] < 1 and s1['bytes'] <= 100000
+    for n in 'ab':
+        x, y = np.load(tmp_path / 's1' / (n + '.npy')), np.load(tmp_path / 's2' / (n + '.npy'))
+        assert np.array_equal(x, y) and x.ndim == 1
+        assert 0 < x.size < np.asarray(arrays[n]).size and np.isin(x, np.asarray(arrays[n]).reshape(-1)).all()
+    assert np.load(tmp_path / 's1' / 'c.npy') == 7                     # small arrays stay whole
+
+
 # ------------------------------------------------------------------ round 4: the feed
 def _varlen_batches(hp, n, seed=3):
     '''host batches [B*C, T_i, F] of different lengths, some real some complex (toy data is

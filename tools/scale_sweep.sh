@@ -19,7 +19,7 @@ for N in 1 2 4 8; do
     # N = 1 takes the same spawn path (a 1-rank RCCL group) so that the curve starts from a
     # run that includes the collective's launch cost
     DANET_FORCE_DIST=1 timeout 900 python bench.py --gpus $N --steps $STEPS --warmup $WARM \
-        --allreduce-schedule $SCHED --no-cpu-baseline --no-parity-check $EXTRA \
+        --full --allreduce-schedule $SCHED --no-cpu-baseline --no-parity-check $EXTRA \
         2> gpurun_out/scale/cfg2_n${N}_sched${SCHED}.err | tail -1 > $OUT
     python - "$OUT" "$N" "$SCHED" <<'PY'
 import json, sys

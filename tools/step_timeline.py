@@ -5,8 +5,8 @@
         python $REPO/bench.py --steps 6 --warmup 3 --no-cpu-baseline
     python tools/step_timeline.py /tmp/tl/.../tl_kernel_trace.csv [step_index [v]]
 
-(bench.py records HIP events only on timed steps 0, 4, 8, ...: pick an un-instrumented one,
-e.g. step_index = warmup + 5.)  Prints, for the chosen step (frontend_kernel to frontend_kernel), every kernel
+(bench.py --full records HIP events only on timed steps 0, 4, 8, ...: pick an un-instrumented one,
+e.g. step_index = warmup + 5; a plain run records none.)  Prints, for the chosen step (frontend_kernel to frontend_kernel), every kernel
 with start offset / duration / queue, the busy time of the union of all kernels and the
 idle gaps (no kernel running at all).'''
 import csv
