@@ -4,7 +4,9 @@ Builds libdanet_hip.so (gfx950 only) in-tree with hipcc.
     python danet-tensorflow_amd/_build.py [--force]
 
 One object per .hip/.cpp under csrc/, compiled in parallel, linked into
-csrc/libdanet_hip.so.  Objects are rebuilt only when their source (or a shared
+csrc/libdanet_hip.so.  The extension library of the conv-bilstm-v1 encoder
+(csrc/conv/*.hip -> csrc/libdanet_conv_hip.so, include/danet_conv_hip.h) is
+built by the same call.  Objects are rebuilt only when their source (or a shared
 header) is newer.  No torch headers are involved: the library is a plain C ABI
 (include/danet_hip.h).
 '''
@@ -18,6 +20,9 @@ CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 BUILD = os.path.join(CSRC, 'build')
 LIB = os.path.join(CSRC, 'libdanet_hip.so')
+CONV_CSRC = os.path.join(CSRC, 'conv')
+CONV_BUILD = os.path.join(CONV_CSRC, 'build')
+CONV_LIB = os.path.join(CSRC, 'libdanet_conv_hip.so')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # -fvisibility=hidden: only what include/danet_hip.h declares (inside its visibility pragma) is exported
@@ -40,9 +45,9 @@ def _headers_mtime():
     return m
 
 
-def _compile(src, force, hdr_m, bdir=BUILD, defs=()):
+def _compile(src, force, hdr_m, bdir=BUILD, defs=(), src_dir=CSRC):
     obj = os.path.join(bdir, os.path.splitext(src)[0] + '.o')
-    sp = os.path.join(CSRC, src)
+    sp = os.path.join(src_dir, src)
     if (not force and os.path.exists(obj)
             and os.path.getmtime(obj) > max(os.path.getmtime(sp), hdr_m)):
         return obj, False
@@ -55,9 +60,9 @@ def _compile(src, force, hdr_m, bdir=BUILD, defs=()):
     return obj, True
 
 
-def _link(objs, out):
+def _link(objs, out, exports=os.path.join(CSRC, 'exports.map')):
     cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC',
-           '-Wl,--version-script=' + os.path.join(CSRC, 'exports.map'), '-o', out] + objs
+           '-Wl,--version-script=' + exports, '-o', out] + objs
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError('link failed:\n%s\n%s' % (r.stdout, r.stderr))
@@ -76,7 +81,26 @@ def build(force=False, verbose=True):
     if verbose:
         print('libdanet_hip.so: %s (%d objects, %s)' % (
             LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
+    build_conv(force=force, verbose=verbose)
     return LIB
+
+
+def build_conv(force=False, verbose=True):
+    '''csrc/conv/*.hip -> csrc/libdanet_conv_hip.so (objects under csrc/conv/build/)'''
+    os.makedirs(CONV_BUILD, exist_ok=True)
+    hdr_m = max([os.path.getmtime(os.path.join(INCLUDE, 'danet_conv_hip.h'))] +
+                [os.path.getmtime(os.path.join(CONV_CSRC, f)) for f in os.listdir(CONV_CSRC) if f.endswith('.h')])
+    srcs = sorted(f for f in os.listdir(CONV_CSRC) if f.endswith('.hip'))
+    with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
+        res = list(ex.map(lambda s: _compile(s, force, hdr_m, CONV_BUILD, src_dir=CONV_CSRC), srcs))
+    objs = [o for o, _ in res]
+    rebuilt = any(r for _, r in res)
+    if rebuilt or not os.path.exists(CONV_LIB):
+        _link(objs, CONV_LIB, exports=os.path.join(CONV_CSRC, 'exports.map'))
+    if verbose:
+        print('libdanet_conv_hip.so: %s (%d objects, %s)' % (
+            CONV_LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
+    return CONV_LIB
 
 
 def build_variant(name, defs):

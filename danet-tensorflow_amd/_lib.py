@@ -151,6 +151,73 @@ def load():
     return _lib
 
 
+# ---- the extension library of the conv-bilstm-v1 encoder (include/danet_conv_hip.h) ----
+# A separate shared object with its own ABI version: the core's table above stays exactly the core
+# header's.  Missing library = hard error, as for the core.
+CONV_LIB_PATH = os.path.join(_HERE, 'csrc', 'libdanet_conv_hip.so')
+CONV_ABI_VERSION = 1
+
+
+class ConvDesc(ctypes.Structure):
+    '''danet_conv_desc_t (include/danet_conv_hip.h)'''
+    _fields_ = [('B', c_int), ('Cin', c_int), ('Cout', c_int), ('T', c_int), ('F', c_int), ('k', c_int),
+                ('pool', c_int), ('d2s', c_int), ('alpha', c_f32),
+                ('x_stride', c_i64 * 4), ('y_stride', c_i64 * 4)]
+
+
+_CD = ctypes.POINTER(ConvDesc)
+# name -> (restype, argtypes); mirrors include/danet_conv_hip.h
+CONV_PROTOTYPES = {
+    'danet_conv_abi_version': (c_int, []),
+    'danet_conv_last_error': (ctypes.c_char_p, []),
+    'danet_conv_workspace_bytes': (c_sz, [c_int, _CD]),
+    'danet_conv_fwd': (c_int, [c_p, _CD, c_p, c_p, c_p, c_p, c_p]),
+    'danet_conv_bwd_data': (c_int, [c_p, _CD, c_p, c_p, c_p, c_p, c_p]),
+    'danet_conv_bwd_weight': (c_int, [c_p, _CD, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_p, c_sz]),
+    'danet_conv_add': (c_int, [c_p, c_i64, c_p, c_p, c_p]),
+}
+CONV_WS_BWD_WEIGHT = 0
+_conv = None
+
+
+def load_conv():
+    '''dlopen libdanet_conv_hip.so (after torch and the core library)'''
+    global _conv
+    if _conv is not None:
+        return _conv
+    with _lock:
+        if _conv is not None:
+            return _conv
+        if not os.path.exists(CONV_LIB_PATH):
+            raise DanetHipError(
+                'libdanet_conv_hip.so not found at %s -- the conv-bilstm-v1 encoder needs the HIP '
+                'extension library (there is no CPU fallback); build it with '
+                '`python -c "import __graft_entry__ as g; g.build()"`' % CONV_LIB_PATH)
+        lib = ctypes.CDLL(CONV_LIB_PATH, mode=ctypes.RTLD_LOCAL)
+        for name, (res, args) in CONV_PROTOTYPES.items():
+            fn = getattr(lib, name)      # AttributeError if the symbol is missing
+            fn.restype = res
+            fn.argtypes = args
+        if lib.danet_conv_abi_version() != CONV_ABI_VERSION:
+            raise DanetHipError('libdanet_conv_hip.so ABI version mismatch')
+        _conv = lib
+    return _conv
+
+
+def conv_check(rc):
+    if rc != 0:
+        msg = load_conv().danet_conv_last_error()
+        raise DanetHipError('libdanet_conv_hip error %d: %s' % (rc, msg.decode() if msg else '?'))
+
+
+def conv_ws_bytes(op, desc):
+    '''danet_conv_workspace_bytes(op, desc)'''
+    n = load_conv().danet_conv_workspace_bytes(op, ctypes.byref(desc))
+    if n == ctypes.c_size_t(-1).value:
+        conv_check(-1)
+    return n
+
+
 # ---- switches ------------------------------------------------------------------
 # USER switches (README): DANET_GEMM_X6, DANET_LSTM_FWD_FUSED, DANET_SIDE_STREAMS, DANET_FEED_MODE,
 # DANET_OVERLAP_ALLREDUCE, DANET_ALLREDUCE_TAIL_RATIO, DANET_MAX_STEPS_IN_FLIGHT, DANET_STATUS_HOST, DANET_FUSE_HEADS,

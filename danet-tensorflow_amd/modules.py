@@ -10,7 +10,8 @@ tensors instead of TF symbolic tensors; every `__call__` runs hand-written HIP
 kernels through `ops` (no CPU fallback).
 
 Extension (defaults = the reference's hard-coded values, app/modules.py:153,
-212,223-242): `hparams.NUM_LSTM_LAYERS`, `hparams.LSTM_HDIM`.
+212,223-242): `hparams.NUM_LSTM_LAYERS`, `hparams.LSTM_HDIM`.  The `conv-bilstm-v1`
+encoder's convolutions run on the extension library libdanet_conv_hip.so.
 '''
 from math import sqrt
 
@@ -183,6 +184,58 @@ class BiLstmEncoder(_RnnEncoderBase):
 
     def _dims(self):
         return hparams.LSTM_HDIM, hparams.NUM_LSTM_LAYERS
+
+
+@hparams.register_encoder('conv-bilstm-v1')
+class ConvBiLstmEncoder(Encoder):
+    '''Experimental CNN-LSTM hybrid network (app/modules.py:263-379): 8 conv layers (2-D
+    convolution, max-pooling and depth-to-space on libdanet_conv_hip.so) around a 2-layer BiLSTM of
+    width FFT_SIZE with a centred residual, then a bias-free dense layer.  The LSTM width and depth
+    are the reference's (FFT_SIZE, 2) whatever LSTM_HDIM / NUM_LSTM_LAYERS say; the number of frames
+    must be a multiple of 4 (LENGTH_ALIGN) and FFT_SIZE a multiple of 8, >= 16.'''
+    def __init__(self, model, name):
+        super(ConvBiLstmEncoder, self).__init__(model, name)
+
+    def _conv_vars(self, scope, k, cin, cout, w_init=None):
+        # tf.layers.conv2d: kernel [k, k, Cin, Cout] (glorot-uniform unless given), bias zeros
+        if w_init is None:
+            w_init = _uniform_init(sqrt(6. / (k * k * (cin + cout))))
+        m = self.model
+        w = m.get_variable('%s/%s/kernel' % (self.name, scope), [k, k, cin, cout], w_init)
+        b = m.get_variable('%s/%s/bias' % (self.name, scope), [cout], _const_init(np.zeros(cout)))
+        return [w, b]
+
+    def __call__(self, s_signals, s_dropout_keep=1.):
+        B, T, F = s_signals.shape
+        nfft, E = hparams.FFT_SIZE, hparams.EMBED_SIZE
+        ops.conv_encoder_check(T, nfft, F)
+        m = self.model
+        w_initer = _uniform_init(2. / sqrt(nfft))                     # modules.py:278-280
+        b_initer = _const_init(_lstm_bias(nfft, i_bias=1.))           # modules.py:282-287
+        conv_w_initer = _uniform_init(3e-1)                            # modules.py:336-338
+        names = ['conv2d'] + ['conv2d_%d' % i for i in range(1, 8)]
+        params = []
+        for i, (cin, cout, k, _, _) in enumerate(ops.CONV_LAYERS[:4]):
+            params += self._conv_vars(names[i], k, cin, cout)
+        for l in range(2):
+            for d in ('_fwd', '_bwd'):
+                base = '%s/lstm%d%s/LSTM/linear/' % (self.name, l, d)
+                params.append(m.get_variable(base + 'W', [2 * nfft + nfft, 4 * nfft], w_initer))
+                params.append(m.get_variable(base + 'B', [4 * nfft], b_initer))
+        for i, (cin, cout, k, _, _) in enumerate(ops.CONV_LAYERS[4:], 4):
+            params += self._conv_vars(names[i], k, cin, cout, conv_w_initer if i < 6 else None)
+        O = F * E
+        params.append(m.get_variable(self.name + '/dense/kernel', [nfft, O],
+                                     _uniform_init(sqrt(6. / (nfft + O)))))
+        debug = {} if hparams.DEBUG else None
+        s_out = ops.ConvBiLstmEncoderFn.apply(s_signals, nfft, float(hparams.RELU_LEAKAGE), debug, *params)
+        if hparams.DEBUG:
+            # the reference's NCHW shapes (copies: debug path only)
+            T4, N8 = T // 4, nfft // 8
+            nchw = lambda t: t.detach().view(T4, B, 16, N8).permute(1, 2, 0, 3).contiguous()
+            self.debug_fetches = dict(conv_act=nchw(debug['conv_act']), lstm_act=nchw(debug['lstm_act']),
+                                      mid4=debug['mid4'].detach().clone())
+        return s_out.reshape(hparams.BATCH_SIZE, -1, F, E)            # modules.py:372-374
 
 
 class _TruthEstimatorBase(Estimator):

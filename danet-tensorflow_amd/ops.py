@@ -8,6 +8,7 @@ follow the reference where a counterpart exists.
 
 Everything here requires the HIP library and a GPU; nothing falls back to CPU.
 '''
+import ctypes
 import itertools
 import math
 
@@ -1280,6 +1281,220 @@ class RnnEncoderFn(torch.autograd.Function):
         join_deferred()
         ctx.ctxs = None
         return (None, None, None, None) + tuple(grads) + (None if direct_out else dWout,)
+
+
+# ---------------------------------------------------------------------------
+# conv-bilstm-v1 encoder (app/modules.py:263-379) on the extension library libdanet_conv_hip.so
+# ---------------------------------------------------------------------------
+def _conv_desc(B, Cin, Cout, T, F, k, alpha, xs, ys, pool=False, d2s=False):
+    d = _lib.ConvDesc()
+    d.B, d.Cin, d.Cout, d.T, d.F, d.k = B, Cin, Cout, T, F, k
+    d.pool, d.d2s, d.alpha = int(pool), int(d2s), float(alpha)
+    for a in range(4):
+        d.x_stride[a], d.y_stride[a] = int(xs[a]), int(ys[a])
+    return d
+
+
+def conv_fwd(d, x, w, b, y, argmax=None):
+    '''y = lrelu(conv(x, w) + b) (+ pool -> argmax | depth-to-space), layouts by d's strides'''
+    with _lib.timed('conv_fwd'):
+        _lib.conv_check(_lib.load_conv().danet_conv_fwd(_lib.stream(), ctypes.byref(d), ptr(_f32(x)), ptr(_f32(w)),
+                                                        ptr(_f32(b)), ptr(_f32(y)), ptr(argmax)))
+    return y
+
+
+def conv_bwd_data(d, dy, y, argmax, w, dx):
+    '''dx = dgrad of layer d from dy (at y's layout), lrelu' from the saved y, pool via argmax'''
+    with _lib.timed('conv_dgrad'):
+        _lib.conv_check(_lib.load_conv().danet_conv_bwd_data(_lib.stream(), ctypes.byref(d), ptr(_f32(dy)),
+                                                             ptr(_f32(y)), ptr(argmax), ptr(_f32(w)), ptr(_f32(dx))))
+    return dx
+
+
+def conv_bwd_weight(d, x, dy, y, argmax, dw, db, accumulate=False):
+    '''dw, db of layer d (accumulate: += into them); deterministic two-pass slab reduction'''
+    need = _lib.conv_ws_bytes(_lib.CONV_WS_BWD_WEIGHT, d)
+    w, wn = _ws(need, dy.device)
+    with _lib.timed('conv_wgrad'):
+        _lib.conv_check(_lib.load_conv().danet_conv_bwd_weight(
+            _lib.stream(), ctypes.byref(d), ptr(_f32(x)), ptr(_f32(dy)), ptr(_f32(y)), ptr(argmax),
+            ptr(_f32(dw)), ptr(_f32(db)), int(bool(accumulate)), ptr(w), wn))
+
+
+def conv_add(a, b, out):
+    '''out = a + b over out.numel() elements (all three dense)'''
+    _lib.conv_check(_lib.load_conv().danet_conv_add(_lib.stream(), out.numel(), ptr(_f32(a)), ptr(_f32(b)),
+                                                    ptr(_f32(out))))
+    return out
+
+
+def conv_encoder_check(T, nfft, F):
+    '''the shapes conv-bilstm-v1 is defined for (ValueError before any launch)'''
+    if nfft % 8 or nfft < 16:
+        raise ValueError('conv-bilstm-v1: FFT_SIZE must be a multiple of 8 and >= 16 (got %d)' % nfft)
+    if F != nfft // 2 + 1:
+        raise ValueError('conv-bilstm-v1: %d bins, FFT_SIZE %d needs %d' % (F, nfft, nfft // 2 + 1))
+    if T % 4:
+        raise ValueError('conv-bilstm-v1: the number of frames must be a multiple of 4 (LENGTH_ALIGN), '
+                         'got %d' % T)
+
+
+# conv layers of the encoder, in creation order: (Cin, Cout, k, pool, depth-to-space)
+CONV_LAYERS = ((1, 8, 5, False, False), (8, 16, 5, True, False), (16, 32, 3, False, False),
+               (32, 16, 3, True, False), (16, 32, 3, False, False), (32, 64, 3, False, True),
+               (16, 16, 5, False, False), (16, 8, 5, False, False))
+
+
+def conv_encoder_descs(B, T, nfft, alpha):
+    '''the 8 layer descriptors, with the layouts that chain them without copies:
+    x [B][T][F] (mix_log) -> a0 [B][8][T][F] -> pool -> p1 [B][16][T/2][nfft/4] -> a2 [B][32][T/2][nfft/4]
+    -> pool -> p3 time-major [T/4][B][16 * nfft/8] (the LSTM's input rows; conv_act and lstm_act alike)
+    lstm_act -> a4 [B][32][T/4][nfft/8] -> depth-to-space -> mid4 [B][16][T/2][nfft/4]
+    -> a6 [B][16][T/2][nfft/4] -> rows [B][T/2][8][nfft/4], which is the dense layer's [B*T][nfft]'''
+    F = nfft // 2 + 1
+    T2, T4, N4, N8 = T // 2, T // 4, nfft // 4, nfft // 8
+    D = 2 * nfft
+    X0 = (T * F, T * F, F, 1)
+    A0 = (8 * T * F, T * F, F, 1)
+    P1 = (16 * T2 * N4, T2 * N4, N4, 1)
+    A2 = (32 * T2 * N4, T2 * N4, N4, 1)
+    TM = (D, N8, B * D, 1)
+    A4 = (32 * T4 * N8, T4 * N8, N8, 1)
+    M4 = (16 * T2 * N4, T2 * N4, N4, 1)
+    RW = (T2 * 8 * N4, N4, 8 * N4, 1)
+    geo = ((T, F, X0, A0), (T, F, A0, P1), (T2, N4, P1, A2), (T2, N4, A2, TM),
+           (T4, N8, TM, A4), (T4, N8, A4, M4), (T2, N4, M4, M4), (T2, N4, M4, RW))
+    return [_conv_desc(B, ci, co, t, f, k, alpha, xs, ys, pool=pool, d2s=d2s)
+            for (ci, co, k, pool, d2s), (t, f, xs, ys) in zip(CONV_LAYERS, geo)]
+
+
+class ConvBiLstmEncoderFn(torch.autograd.Function):
+    '''Whole `conv-bilstm-v1` encoder (app/modules.py:263-379): conv2d .. conv2d_3 (two fused 2x2
+    max-pools) -> centre (conv_act) -> 2 BiLSTM layers of width nfft -> + conv_act -> centre
+    (lstm_act) -> conv2d_4, conv2d_5 (+ depth-to-space), conv2d_6, conv2d_7 -> bias-free dense.
+    x [B,T,F] (T % 4 == 0) -> embed [B,T,O].  Every step is a library kernel; the layers hand
+    each other their layouts through strides (conv_encoder_descs), so there are no copies.
+    params = (w0, b0, .., w3, b3, W_0f, b_0f, W_0b, b_0b, W_1f, b_1f, W_1b, b_1b, w4, b4, .., w7, b7,
+    W_dense).  debug: None or a dict that receives conv_act, lstm_act (time-major [T/4][B][2 nfft])
+    and mid4 ([B][16][T/2][nfft/4]).'''
+
+    @staticmethod
+    def forward(ctx, x, nfft, alpha, debug, *params):
+        x = _f32(x.contiguous())
+        B, T, F = x.shape
+        conv_encoder_check(T, nfft, F)
+        dev = x.device
+        T2, T4, N4, N8 = T // 2, T // 4, nfft // 4, nfft // 8
+        H, D = nfft, 2 * nfft
+        ds = conv_encoder_descs(B, T, nfft, alpha)
+        cw = [(params[2 * l], params[2 * l + 1]) for l in range(4)] + \
+             [(params[16 + 2 * l], params[17 + 2 * l]) for l in range(4)]
+        lp = params[8:16]
+        Wd = params[24]
+        O = Wd.shape[1]
+        # output buffers + workspaces of both recurrent launches (a train step: + the BPTT rings), ONE fill
+        ypads = [torch.empty(T4 + 2, B, D, device=dev) for _ in range(2)]
+        wss = [_lstm_ws(T4, B, H, 2, dev)[0] for _ in range(2)]
+        bwss = None
+        if any(ctx.needs_input_grad) and BWD_DB and _L().danet_lstm_bwd_db_supported(T4, B, H, 2) == 1:
+            bwss = [_lstm_ws(T4, B, H, 2, dev)[0] for _ in range(2)]
+        if bwss is None or not lstm_prefill_train(T4, B, H, 2, ypads, wss, bwss):
+            bwss = None
+            lstm_prefill_fwd(T4, B, D, ypads, wss)
+        u8 = torch.uint8
+        a0 = conv_fwd(ds[0], x, *cw[0], torch.empty(B, 8, T, F, device=dev))            # modules.py:290-293
+        am1 = torch.empty(B, 16, T2, N4, dtype=u8, device=dev)
+        p1 = conv_fwd(ds[1], a0, *cw[1], torch.empty(B, 16, T2, N4, device=dev), am1)    # :294-300
+        a2 = conv_fwd(ds[2], p1, *cw[2], torch.empty(B, 32, T2, N4, device=dev))         # :302-305
+        am3 = torch.empty(B, 16, T4, N8, dtype=u8, device=dev)
+        p3 = conv_fwd(ds[3], a2, *cw[3], torch.empty(T4, B, D, device=dev), am3)         # :306-311
+        conv_act = torch.empty(T4, B, D, device=dev)
+        center(p3, B, T4, D, 1, D, conv_act, 1, D)                                       # :313
+        c0 = lstm_layer_fwd(conv_act, D, D, T4, B, H, list(lp[0:4:2]), list(lp[1:4:2]),  # :315-324
+                            ypad=ypads[0], ws=wss[0])
+        c1 = lstm_layer_fwd(c0.ypad[1:], D, D, T4, B, H, list(lp[4:8:2]), list(lp[5:8:2]),  # :325-329
+                            ypad=ypads[1], ws=wss[1])
+        s = conv_add(c1.ypad[1:T4 + 1], conv_act, torch.empty(T4, B, D, device=dev))     # :333
+        lstm_act = torch.empty(T4, B, D, device=dev)
+        center(s, B, T4, D, 1, D, lstm_act, 1, D)                                        # :334
+        a4 = conv_fwd(ds[4], lstm_act, *cw[4], torch.empty(B, 32, T4, N8, device=dev))   # :339-343
+        mid4 = conv_fwd(ds[5], a4, *cw[5], torch.empty(B, 16, T2, N4, device=dev))       # :344-353
+        a6 = conv_fwd(ds[6], mid4, *cw[6], torch.empty(B, 16, T2, N4, device=dev))       # :355-358
+        rows = conv_fwd(ds[7], a6, *cw[7], torch.empty(B * T, nfft, device=dev))         # :359-366
+        embed = torch.empty(B, T, O, device=dev)
+        if _x6_ok(B * T, O, (rows, nfft, nfft)):                                         # :369-371
+            gemm_w(rows, nfft, Wd, 1, O, embed, B * T, O, nfft, O, tag='proj')
+        else:
+            gemm(rows, Wd, embed, B * T, O, nfft, nfft, O, O, tag='proj')
+        if debug is not None:
+            debug.update(conv_act=conv_act, lstm_act=lstm_act, mid4=mid4)
+        ctx.bwss = bwss
+        ctx.ds, ctx.cw, ctx.Wd = ds, cw, Wd
+        ctx.acts = (x, a0, p1, am1, a2, p3, am3, lstm_act, a4, mid4, a6, rows)
+        ctx.lstm = (c0, c1)
+        ctx.dims = (B, T, F, nfft, O)
+        return embed
+
+    @staticmethod
+    def backward(ctx, dembed):
+        B, T, F, nfft, O = ctx.dims
+        T4, D = T // 4, 2 * nfft
+        dembed = _f32(dembed.contiguous())
+        dev = dembed.device
+        ds, cw, Wd = ctx.ds, ctx.cw, ctx.Wd
+        x, a0, p1, am1, a2, p3, am3, lstm_act, a4, mid4, a6, rows = ctx.acts
+        grads = [None] * 25
+
+        def conv_bwd(l, xin, y, am, dy, dx):
+            w, b = cw[l]
+            if dx is not None:                       # the critical path first
+                conv_bwd_data(ds[l], dy, y, am, w, dx)
+            gw, okw = _grad_target(w, tuple(w.shape), dev)
+            gb, okb = _grad_target(b, tuple(b.shape), dev)
+            direct = okw and okb
+            if not direct:
+                gw, gb = torch.empty(*w.shape, device=dev), torch.empty(*b.shape, device=dev)
+                i = 2 * l if l < 4 else 16 + 2 * (l - 4)
+                grads[i], grads[i + 1] = gw, gb
+            conv_bwd_weight(ds[l], xin, dy, y, am, gw, gb, accumulate=direct)
+            return dx
+
+        # dense (modules.py:369-371): drows = dembed Wd^T, dWd = rows^T dembed
+        drows = torch.empty(B * T, nfft, device=dev)
+        if _x6_ok(B * T, nfft, (dembed, O, O)):
+            gemm_w(dembed, O, Wd, O, 1, drows, B * T, nfft, O, nfft, tag='dYc')
+        else:
+            gemm(dembed, Wd, drows, B * T, nfft, O, O, O, nfft, transB=True, tag='dYc')
+        dWd, okd = _grad_target(Wd, (nfft, O), dev)
+        gemm(rows, dembed, dWd, nfft, O, B * T, nfft, O, O, transA=True, beta=1.0 if okd else 0.0, tag='dWout')
+        grads[24] = None if okd else dWd
+        da6 = conv_bwd(7, a6, rows, None, drows, torch.empty(a6.shape, device=dev))
+        dmid4 = conv_bwd(6, mid4, a6, None, da6, torch.empty(a6.shape, device=dev))
+        da4 = conv_bwd(5, a4, mid4, None, dmid4, torch.empty(a4.shape, device=dev))
+        dla = conv_bwd(4, lstm_act, a4, None, da4, torch.empty(T4, B, D, device=dev))
+        # lstm_act = centre(y1 + conv_act): both branches get centre(dla) (centring is self-adjoint)
+        g = torch.empty(T4, B, D, device=dev)
+        center(dla, B, T4, D, 1, D, g, 1, D)
+        bwss = ctx.bwss if ctx.bwss is not None else [None, None]
+        ctx.bwss = None
+        c0, c1 = ctx.lstm
+        dy = g
+        for l, c in ((1, c1), (0, c0)):
+            dx, dWs, dbs = lstm_layer_bwd(c, dy, need_dx=True, is_top=(l == 1), ws_prefilled=bwss[l])
+            for d in range(2):
+                grads[8 + 4 * l + 2 * d], grads[9 + 4 * l + 2 * d] = dWs[d], dbs[d]
+            dy = dx
+        # conv_act feeds lstm0 and the residual: its gradient is the sum, then centring's backward
+        dca = conv_add(dy, g, torch.empty(T4, B, D, device=dev))
+        dp3 = torch.empty(T4, B, D, device=dev)
+        center(dca, B, T4, D, 1, D, dp3, 1, D)
+        da2 = conv_bwd(3, a2, p3, am3, dp3, torch.empty(a2.shape, device=dev))
+        dp1 = conv_bwd(2, p1, a2, None, da2, torch.empty(p1.shape, device=dev))
+        da0 = conv_bwd(1, a0, p1, am1, dp1, torch.empty(a0.shape, device=dev))
+        conv_bwd(0, x, a0, None, da0, None)
+        join_deferred()
+        ctx.acts = ctx.lstm = None
+        return (None, None, None, None) + tuple(grads)
 
 
 class LinearFn(torch.autograd.Function):
