@@ -18,6 +18,7 @@
  *   pool = 1: 2x2 max-pool, stride 2, 'valid' (Tp = T/2, Fp = F/2 rounded down); `y` holds the
  *             pooled [B][Cout][Tp][Fp] (at y_stride) and `argmax` (uint8, dense [B][Cout][Tp][Fp])
  *             the window position of the first maximum in row-major order (0..3 = 2*dt + df).
+ *             A NaN reaches the pooled output only when it is the first element of its window.
  *   d2s = 1:  depth-to-space by 2: y_stride addresses a [B][Cout/4][2T][2F] tensor and
  *             out[c][2t+a][2f+b] = z[4c+2a+b][t][f] (Cout % 4 == 0).
  * Products are exact fp32 (v_mfma_f32_16x16x4_f32) with fp32 accumulation.

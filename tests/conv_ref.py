@@ -21,11 +21,12 @@ def conv(x, w, b, alpha, pool=False):
     return Fn.max_pool2d(y, 2, 2) if pool else y
 
 
-def depth_to_space(x, nfft):
-    '''modules.py:350-358: [B, 64, T/4, nfft/8] -> [B, 16, T/2, nfft/4]'''
-    B = x.shape[0]
-    x = x.reshape(B, 16, 2, 2, -1, nfft // 8).permute(0, 1, 4, 2, 5, 3)
-    return x.reshape(B, 16, -1, nfft // 4)
+def depth_to_space(x):
+    '''modules.py:350-358, block 2: [B, C, T, F] -> [B, C/4, 2T, 2F] with
+    out[c][2t+a][2f+b] = x[4c+2a+b][t][f] (the encoder: [B, 64, T/4, nfft/8] -> [B, 16, T/2, nfft/4])'''
+    B, C, T, F = x.shape
+    x = x.reshape(B, C // 4, 2, 2, T, F).permute(0, 1, 4, 2, 5, 3)
+    return x.reshape(B, C // 4, 2 * T, 2 * F)
 
 
 def _center(x):
@@ -56,7 +57,7 @@ def encoder(x, params, nfft, E, alpha, fetches=None):
     s_mid3 = s.reshape(B, -1, 16, nfft // 8).transpose(1, 2)
     s_mid3 = _center(s_mid3 + s_mid1)
     h = c(s_mid3, 4)
-    mid4 = depth_to_space(c(h, 5), nfft)
+    mid4 = depth_to_space(c(h, 5))
     h = c(mid4, 6)
     h = c(h, 7)                                                          # [B, 8, T/2, nfft/4]
     rows = h.transpose(1, 2).reshape(B, -1, nfft)
