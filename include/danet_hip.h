@@ -301,7 +301,8 @@ int danet_colsum_f32(danet_stream_t stream, int M, int N, const float* A,
  * all workgroups of the launch co-resident (checked: <= the device's CU count).
  * The call first fills ypad blocks 1..T with the bit pattern 0xFFFFFFFF ("not
  * yet published": the exchanged state is its own flag), so ypad must not be
- * read concurrently.
+ * read concurrently.  The fill covers whole blocks: with ldy > ndir*H the gap
+ * columns [ndir*H, ldy) of every block of ypad are overwritten too.
  * Hand-off status: `status` is an optional caller-owned DEVICE int32 that the
  * kernels set non-zero when a bounded inter-workgroup wait timed out (the
  * outputs of that launch are then invalid).  It is STICKY: the library never
@@ -384,8 +385,9 @@ int danet_lstm_fwd_fused(danet_stream_t stream, int T, int B, int H, int ndir,
  * sum_{t,b} da_d, overwritten for beta = 0, accumulated into for beta = 1 -- the
  * owner threads of the reduce-scatter kernel add their da to a register per step, so
  * no column-sum launches are needed (NULL: the caller may use danet_colsum_f32 on da).
- * Envelope = the reduce-scatter geometry (one workgroup per CU: at H = 300 up to B = 200,
- * at H = 600 up to B = 96, both directions); danet_lstm_bwd_db_supported() == 1 inside
+ * Envelope = the reduce-scatter geometry (one workgroup per CU; on 256 CUs the largest B is
+ * 192 / 400 at H = 300 and 96 / 208 at H = 600 for ndir = 2 / 1; it is wider than the
+ * forward's at some shapes); danet_lstm_bwd_db_supported() == 1 inside
  * it, DANET_ERR_UNSUPPORTED outside.  With DANET_LSTM_DB_DEFERRED in
  * `flags` db is not touched by this call: danet_lstm_bwd_db_reduce finishes it on any
  * stream ordered behind the launch.                                             */

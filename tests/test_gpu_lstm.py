@@ -155,7 +155,7 @@ def test_lstm_fused_envelope_query(monkeypatch):
     assert L.danet_lstm_fwd_fused_supported(128, 32, 300, 2, 600) == 1      # default: B >= 24
     assert L.danet_lstm_fwd_fused_supported(1251, 1, 300, 2, 600) == 0      # B = 1: hoisted GEMM
     assert L.danet_lstm_bwd_db_supported(128, 32, 300, 2) == 1              # reduce-scatter BPTT
-    assert L.danet_lstm_bwd_db_supported(128, 32, 302, 2) == 0              # H % 4 != 0: all-gather kernel
+    assert L.danet_lstm_bwd_db_supported(128, 32, 302, 2) == 0              # H % 4 != 0: outside every recurrent kernel's envelope
     _lib.set_option('lstm_fwd_fused', 1)
     assert L.danet_lstm_fwd_fused_supported(1251, 1, 300, 2, 600) == 1
     assert L.danet_lstm_fwd_fused_supported(128, 32, 300, 2, 129) == 1
