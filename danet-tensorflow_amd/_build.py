@@ -6,7 +6,8 @@ Builds libdanet_hip.so (gfx950 only) in-tree with hipcc.
 One object per .hip/.cpp under csrc/, compiled in parallel, linked into
 csrc/libdanet_hip.so.  The extension library of the conv-bilstm-v1 encoder
 (csrc/conv/*.hip -> csrc/libdanet_conv_hip.so, include/danet_conv_hip.h) is
-built by the same call.  Objects are rebuilt only when their source (or a shared
+built by the same call, and so is the dropout extension (csrc/dropout/*.hip ->
+csrc/libdanet_dropout_hip.so, include/danet_dropout_hip.h).  Objects are rebuilt only when their source (or a shared
 header) is newer.  No torch headers are involved: the library is a plain C ABI
 (include/danet_hip.h).
 '''
@@ -23,6 +24,9 @@ LIB = os.path.join(CSRC, 'libdanet_hip.so')
 CONV_CSRC = os.path.join(CSRC, 'conv')
 CONV_BUILD = os.path.join(CONV_CSRC, 'build')
 CONV_LIB = os.path.join(CSRC, 'libdanet_conv_hip.so')
+DROPOUT_CSRC = os.path.join(CSRC, 'dropout')
+DROPOUT_BUILD = os.path.join(DROPOUT_CSRC, 'build')
+DROPOUT_LIB = os.path.join(CSRC, 'libdanet_dropout_hip.so')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # -fvisibility=hidden: only what include/danet_hip.h declares (inside its visibility pragma) is exported
@@ -82,6 +86,7 @@ def build(force=False, verbose=True):
         print('libdanet_hip.so: %s (%d objects, %s)' % (
             LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
     build_conv(force=force, verbose=verbose)
+    build_dropout(force=force, verbose=verbose)
     return LIB
 
 
@@ -101,6 +106,22 @@ def build_conv(force=False, verbose=True):
         print('libdanet_conv_hip.so: %s (%d objects, %s)' % (
             CONV_LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
     return CONV_LIB
+
+
+def build_dropout(force=False, verbose=True):
+    '''csrc/dropout/*.hip -> csrc/libdanet_dropout_hip.so (objects under csrc/dropout/build/)'''
+    os.makedirs(DROPOUT_BUILD, exist_ok=True)
+    hdr_m = os.path.getmtime(os.path.join(INCLUDE, 'danet_dropout_hip.h'))
+    srcs = sorted(f for f in os.listdir(DROPOUT_CSRC) if f.endswith('.hip'))
+    res = [_compile(s, force, hdr_m, DROPOUT_BUILD, src_dir=DROPOUT_CSRC) for s in srcs]
+    objs = [o for o, _ in res]
+    rebuilt = any(r for _, r in res)
+    if rebuilt or not os.path.exists(DROPOUT_LIB):
+        _link(objs, DROPOUT_LIB, exports=os.path.join(DROPOUT_CSRC, 'exports.map'))
+    if verbose:
+        print('libdanet_dropout_hip.so: %s (%d objects, %s)' % (
+            DROPOUT_LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
+    return DROPOUT_LIB
 
 
 def build_variant(name, defs):

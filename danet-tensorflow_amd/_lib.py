@@ -218,6 +218,51 @@ def conv_ws_bytes(op, desc):
     return n
 
 
+# ---- the dropout extension library (include/danet_dropout_hip.h) ----
+# Loaded at the first call with keep < 1 only: a run with DROPOUT_KEEP_PROB = 1 never maps it.
+DROPOUT_LIB_PATH = os.path.join(_HERE, 'csrc', 'libdanet_dropout_hip.so')
+DROPOUT_ABI_VERSION = 1
+c_u32 = ctypes.c_uint32
+# name -> (restype, argtypes); mirrors include/danet_dropout_hip.h
+DROPOUT_PROTOTYPES = {
+    'danet_dropout_abi_version': (c_int, []),
+    'danet_dropout_last_error': (ctypes.c_char_p, []),
+    'danet_dropout_apply': (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_u32, c_f32, c_u32, c_u32,
+                                    c_u32, c_u32]),
+}
+_dropout = None
+
+
+def load_dropout():
+    '''dlopen libdanet_dropout_hip.so (after torch and the core library)'''
+    global _dropout
+    if _dropout is not None:
+        return _dropout
+    with _lock:
+        if _dropout is not None:
+            return _dropout
+        if not os.path.exists(DROPOUT_LIB_PATH):
+            raise DanetHipError(
+                'libdanet_dropout_hip.so not found at %s -- DROPOUT_KEEP_PROB < 1 needs the HIP '
+                'extension library (there is no CPU fallback); build it with '
+                '`python -c "import __graft_entry__ as g; g.build()"`' % DROPOUT_LIB_PATH)
+        lib = ctypes.CDLL(DROPOUT_LIB_PATH, mode=ctypes.RTLD_LOCAL)
+        for name, (res, args) in DROPOUT_PROTOTYPES.items():
+            fn = getattr(lib, name)      # AttributeError if the symbol is missing
+            fn.restype = res
+            fn.argtypes = args
+        if lib.danet_dropout_abi_version() != DROPOUT_ABI_VERSION:
+            raise DanetHipError('libdanet_dropout_hip.so ABI version mismatch')
+        _dropout = lib
+    return _dropout
+
+
+def dropout_check(rc):
+    if rc != 0:
+        msg = load_dropout().danet_dropout_last_error()
+        raise DanetHipError('libdanet_dropout_hip error %d: %s' % (rc, msg.decode() if msg else '?'))
+
+
 # ---- switches ------------------------------------------------------------------
 # USER switches (README): DANET_GEMM_X6, DANET_LSTM_FWD_FUSED, DANET_SIDE_STREAMS, DANET_FEED_MODE,
 # DANET_OVERLAP_ALLREDUCE, DANET_ALLREDUCE_TAIL_RATIO, DANET_MAX_STEPS_IN_FLIGHT, DANET_STATUS_HOST, DANET_FUSE_HEADS,

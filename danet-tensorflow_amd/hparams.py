@@ -12,6 +12,11 @@ unchanged.  Differences, all deliberate:
   `scipy.signal.windows.hann`.
 * Two keys are added with the reference's hard-coded values as defaults
   (`app/modules.py:212,223-242`): `NUM_LSTM_LAYERS=4`, `LSTM_HDIM=300`.
+* `DROPOUT_KEEP_PROB` reaches the encoder: the reference feeds it on every train
+  step (`main.py:429`) but calls the encoder without it (`main.py:243`); here
+  `Model.train_step` passes it on and the BiLSTM encoders apply
+  `tf.nn.dropout` where `_lyr_bilstm` has it (`app/modules.py:137`).  The
+  default 1.0 is exactly the reference's behaviour.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''

@@ -51,10 +51,17 @@ class Model(object):
         self.s_states_di = {}
         self.vars = {}
         self._order = []
+        self.seed = int(seed)
         self._gen = torch.Generator().manual_seed(seed)
+        self._dropout = None
         self._flat = None
         self.learn_rate = float(hparams.LR)
         self.step_count = 0
+        # train steps taken before the parameter file this model was loaded from was written: the
+        # dropout masks' `step` word is step_base + step_count, so a resumed run continues the mask
+        # sequence, while Adam's own step (step_count) restarts with its moments, which are not in
+        # the file (trainables only, like the reference's Saver)
+        self.step_base = 0
         self.built = False
         # True: gradients stay readable after train_step (grad_dict); costs one fill
         # kernel per step.  False: the optimiser kernel zeroes them after use.
@@ -266,8 +273,21 @@ class Model(object):
         self.early_steps += 1
 
     # -------------------------------------------------------------- forward
-    def forward(self, s_src_signals, with_valid=False, with_train=True, fuse_heads=False):
+    def dropout_spec(self, keep):
+        '''the ops.DropoutSpec of the step being built: Philox key (seed & 0xffffffff, data-parallel
+        rank), step = step_base + step_count at the start of the step.  One spec per forward pass
+        (Model.forward resets it), shared by every dropout site so their stream ids differ.'''
+        if self._dropout is None or self._dropout.keep != float(keep):
+            self._dropout = ops.DropoutSpec(keep, self.seed & 0xffffffff, dist.rank(),
+                                            self.step_base + self.step_count)
+        return self._dropout
+
+    def forward(self, s_src_signals, with_valid=False, with_train=True, fuse_heads=False,
+                s_dropout_keep=1.0):
         '''main.py:215-337.  s_src_signals complex64 [B, C, T, F].
+        s_dropout_keep: the keep probability the encoder is called with (the reference feeds
+        hparams.DROPOUT_KEEP_PROB on train steps and 1.0 otherwise, main.py:429,490,520, but
+        drops it at main.py:243; here it reaches the encoder).  1.0: no dropout, today's path.
         fuse_heads (train_step): separator + phase re-attach + PIT loss + SNR run as ONE
         kernel forward and ONE backward (ops.SeparatePitFn); the separated magnitudes then
         exist only in registers and `sep_pwr` is not in the returned dict.  Needs a separator
@@ -276,7 +296,11 @@ class Model(object):
         B, E = hparams.BATCH_SIZE, hparams.EMBED_SIZE
         eps = float(hparams.EPS)
         fe = ops.frontend(s_src_signals)                       # main.py:233-240
-        s_embed = self.encoder(fe['mix_log'])                  # main.py:243
+        self._dropout = None
+        if s_dropout_keep < 1.0:
+            s_embed = self.encoder(fe['mix_log'], s_dropout_keep)
+        else:
+            s_embed = self.encoder(fe['mix_log'])              # main.py:243
         s_embed_flat = s_embed.reshape(B, -1, E)               # main.py:244-246
         out = dict(embed=s_embed, input=s_src_signals)
         phasor = fe['phasor']
@@ -340,7 +364,8 @@ class Model(object):
         chain = ops.heads_chain()        # small finalize kernels go to the side stream (ops.py)
         chain.__enter__()
         try:
-            out = self.forward(s_src_signals, fuse_heads=self.fuse_heads)
+            out = self.forward(s_src_signals, fuse_heads=self.fuse_heads,
+                               s_dropout_keep=float(hparams.DROPOUT_KEEP_PROB))    # main.py:429
         except BaseException:
             chain.__exit__(None, None, None)
             ops.drop_lazy(self.device)     # this step's queued finalizers must not run in the next
@@ -443,13 +468,16 @@ class Model(object):
     def save_params(self, filename, step=None):
         '''trainable variables only, like tf.train.Saver(var_list=trainables)
         (main.py:357,399); stored as .npz keyed by the reference's TF variable
-        names (a TF1 checkpoint cannot be written without TF).'''
+        names (a TF1 checkpoint cannot be written without TF).  One extra entry, `step_count`:
+        the number of train steps taken (over all resumed runs), which is also the `step` word of the dropout masks --
+        a run resumed from the file continues the mask sequence.'''
         save_dir = os.path.dirname(os.path.abspath(filename))
         if not os.path.exists(save_dir):
             os.makedirs(save_dir)
         if step is not None:
             filename = '%s-%d' % (filename, step)
-        np.savez(filename, **{k: v.detach().cpu().numpy() for k, v in self.vars.items()})
+        np.savez(filename, step_count=np.int64(self.step_base + self.step_count),
+                 **{k: v.detach().cpu().numpy() for k, v in self.vars.items()})
 
     def load_params(self, filename):
         if not filename.endswith('.npz'):
@@ -458,6 +486,8 @@ class Model(object):
         with torch.no_grad():
             for k, v in self.vars.items():
                 v.copy_(torch.as_tensor(data[k]).to(self.device))
+        if 'step_count' in data.files:       # (files written before the entry existed: unchanged)
+            self.step_base = int(data['step_count']) - self.step_count
         return True
 
     def weights_written(self):

@@ -11,7 +11,8 @@ kernels through `ops` (no CPU fallback).
 
 Extension (defaults = the reference's hard-coded values, app/modules.py:153,
 212,223-242): `hparams.NUM_LSTM_LAYERS`, `hparams.LSTM_HDIM`.  The `conv-bilstm-v1`
-encoder's convolutions run on the extension library libdanet_conv_hip.so.
+encoder's convolutions run on the extension library libdanet_conv_hip.so; the BiLSTM
+encoders' dropout (`s_dropout_keep` < 1) on libdanet_dropout_hip.so.
 '''
 from math import sqrt
 
@@ -89,7 +90,8 @@ def _lstm_bias(hdim, i_bias=1.5):
 
 @hparams.register_encoder('toy')
 class ToyEncoder(Encoder):
-    '''2-layer MLP for debugging (app/modules.py:96-116)'''
+    '''2-layer MLP for debugging (app/modules.py:96-116); s_dropout_keep is accepted and ignored,
+    as in the reference'''
     def __init__(self, model, name):
         super(ToyEncoder, self).__init__(model, name)
 
@@ -113,9 +115,10 @@ class ToyEncoder(Encoder):
 def _lyr_bilstm(name_, model_, s_input_, hdim_, t_axis_, axis_, w_init_, b_init_,
                 s_dropout_keep_):
     '''one bidirectional layer on a batch-major tensor (app/modules.py:120-137);
-    fwd and reversed-bwd scans run concurrently in one persistent launch.
-    Dropout is the identity: the reference never wires keep_prob in
-    (main.py:243) and its default is 1.'''
+    fwd and reversed-bwd scans run concurrently in one persistent launch, then
+    `tf.nn.dropout(s_output, keep_prob)` (app/modules.py:137) as inverted dropout on
+    libdanet_dropout_hip.so when s_dropout_keep_ < 1 (the mask: `model_.dropout_spec`,
+    one stream id per call in call order).  With keep 1 there is no dropout launch.'''
     assert t_axis_ in (-2, 1) and axis_ in (-1, 2)
     D = s_input_.shape[-1]
     params = []
@@ -123,7 +126,13 @@ def _lyr_bilstm(name_, model_, s_input_, hdim_, t_axis_, axis_, w_init_, b_init_
         W = model_.get_variable('%s%s/LSTM/linear/W' % (name_, d), [D + hdim_, 4 * hdim_], w_init_)
         b = model_.get_variable('%s%s/LSTM/linear/B' % (name_, d), [4 * hdim_], b_init_)
         params += [W, b]
-    return ops.LstmLayerFn.apply(s_input_, hdim_, *params)
+    with ops.dropout_scope(_dropout_spec(model_, s_dropout_keep_)):
+        return ops.LstmLayerFn.apply(s_input_, hdim_, *params)
+
+
+def _dropout_spec(model, keep):
+    '''the step's ops.DropoutSpec for keep < 1 (Model.dropout_spec: seed, rank, step), else None'''
+    return model.dropout_spec(keep) if float(keep) < 1. else None
 
 
 class _RnnEncoderBase(Encoder):
@@ -150,14 +159,17 @@ class _RnnEncoderBase(Encoder):
             D = self.NDIR * hdim
         params.append(m.get_variable(self.name + '/output/W', [D, F * E],
                                      _uniform_init(1.85)))  # modules.py:184-191 / :248-255
-        s_out = ops.RnnEncoderFn.apply(s_signals, hdim, nlayer, self.NDIR, *params)
+        # (NDIR == 1, `lstm-orig`: accepted and ignored, as in the reference's class)
+        with ops.dropout_scope(_dropout_spec(m, s_dropout_keep) if self.NDIR == 2 else None):
+            s_out = ops.RnnEncoderFn.apply(s_signals, hdim, nlayer, self.NDIR, *params)
         return s_out.reshape(hparams.BATCH_SIZE, -1, F, E)  # modules.py:192-195 / :256-259
 
 
 @hparams.register_encoder('lstm-orig')
 class LstmEncoder(_RnnEncoderBase):
     '''unidirectional LSTM stack as in the original paper (app/modules.py:140-196);
-    reference shape 4 x 600'''
+    reference shape 4 x 600.  s_dropout_keep is accepted and ignored: the reference builds this
+    stack from model.lyr_lstm, which has no dropout'''
     NDIR = 1
     INIT_SCALE = 1.15
 
@@ -228,7 +240,8 @@ class ConvBiLstmEncoder(Encoder):
         params.append(m.get_variable(self.name + '/dense/kernel', [nfft, O],
                                      _uniform_init(sqrt(6. / (nfft + O)))))
         debug = {} if hparams.DEBUG else None
-        s_out = ops.ConvBiLstmEncoderFn.apply(s_signals, nfft, float(hparams.RELU_LEAKAGE), debug, *params)
+        with ops.dropout_scope(_dropout_spec(m, s_dropout_keep)):
+            s_out = ops.ConvBiLstmEncoderFn.apply(s_signals, nfft, float(hparams.RELU_LEAKAGE), debug, *params)
         if hparams.DEBUG:
             # the reference's NCHW shapes (copies: debug path only)
             T4, N8 = T // 4, nfft // 8

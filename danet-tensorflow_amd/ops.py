@@ -387,6 +387,77 @@ class _LayerCtx(object):
                  'Ws', 'bs')
 
 
+# ---- inverted dropout behind the BiLSTM layers (app/modules.py:137) ------------------------------
+# On the extension library libdanet_dropout_hip.so (include/danet_dropout_hip.h).  The mask is never
+# stored: it is a pure function of (key0, key1, stream_id, step, logical element index), so the
+# backward pass -- and a float64 restatement on another machine -- regenerate it.
+def dropout_threshold(keep):
+    '''keep probability -> the 32-bit threshold an element's Philox word is compared with'''
+    return min(0xffffffff, int(float(keep) * 4294967296.0))
+
+
+def dropout_scale(keep):
+    '''float32(1 / keep): one double division, rounded once'''
+    return ctypes.c_float(1.0 / float(keep)).value
+
+
+class DropoutSpec(object):
+    '''What one model step's dropout masks are drawn from: keep probability, Philox key
+    (key0 = the model's seed, key1 = the data-parallel rank), `step` (the train step's index) --
+    and a counter that hands out stream ids, one per BiLSTM layer in creation order, so a layer
+    draws the same stream in its forward and its backward pass.'''
+    __slots__ = ('keep', 'key0', 'key1', 'step', 'threshold', 'scale', '_next')
+
+    def __init__(self, keep, key0=0, key1=0, step=0):
+        keep = float(keep)
+        if not 0.0 < keep <= 1.0:
+            raise ValueError('dropout keep probability must lie in (0, 1], got %r' % keep)
+        self.keep = keep
+        self.key0, self.key1, self.step = int(key0) & 0xffffffff, int(key1) & 0xffffffff, int(step) & 0xffffffff
+        self.threshold, self.scale = dropout_threshold(keep), dropout_scale(keep)
+        self._next = 0
+
+    @property
+    def active(self):
+        return self.keep < 1.0
+
+    def take(self, n=1):
+        '''the first of `n` consecutive fresh stream ids'''
+        first = self._next
+        self._next += n
+        return first
+
+
+def dropout_apply(x, y, rows, cols, ldx, ldy, spec, stream_id):
+    '''y[r][c] = x[r][c] * scale where the (spec, stream_id) mask keeps logical element r * cols + c,
+    else 0 (danet_dropout_apply; y may be x).  Forward and backward are this same call.'''
+    with _lib.timed('dropout'):
+        _lib.dropout_check(_lib.load_dropout().danet_dropout_apply(
+            _lib.stream(), rows, cols, ptr(_f32(x)), ldx, ptr(_f32(y)), ldy, spec.threshold, spec.scale,
+            spec.key0, spec.key1, stream_id, spec.step))
+    return y
+
+
+_dropout_cur = [None]
+
+
+class dropout_scope(object):
+    '''with ops.dropout_scope(spec): the BiLSTM layers applied inside (LstmLayerFn with two directions,
+    RnnEncoderFn with ndir == 2, ConvBiLstmEncoderFn) drop their outputs by `spec`; None or
+    keep == 1: today's path, no launch, no allocation, the extension library stays unloaded.'''
+
+    def __init__(self, spec):
+        self.spec = spec if (spec is not None and spec.active) else None
+
+    def __enter__(self):
+        self.prev, _dropout_cur[0] = _dropout_cur[0], self.spec
+        return self.spec
+
+    def __exit__(self, *exc):
+        _dropout_cur[0] = self.prev
+        return False
+
+
 # ---- hand-off status of the persistent kernels + bounded host run-ahead -------
 # ONE sticky 4-byte word per device (include/danet_hip.h: `status` of danet_lstm_fwd/bwd):
 # the kernels store DANET_STATUS_TIMEOUT (the bit pattern of 1.0f) into it when a bounded
@@ -697,7 +768,7 @@ class _Fork(object):
     '''with _Fork(dev, n) as f:  f.run(i, fn)  -> fn runs on chain i
     (chain 0 = the current stream, chain i>0 = side stream i-1); join on exit.'''
 
-    def __init__(self, dev, nchains, defer=False, keep=(), lazy=False, event=None):
+    def __init__(self, dev, nchains, defer=False, keep=(), lazy=False, event=None, spacer=False):
         '''defer=True: do not join on exit -- the side chains keep running under
         whatever the main stream does next (e.g. weight-gradient GEMMs under the
         next layer's latency-bound BPTT kernel, which leaves most CUs idle);
@@ -708,7 +779,9 @@ class _Fork(object):
         (an event record is a ~7 us bubble in front of the next kernel); only for forks whose
         main-stream work comes AFTER their side chains.
         event: a ForkEvent already attached to the last launch the side chains have to wait for
-        (then no event is recorded at all).'''
+        (then no event is recorded at all).
+        spacer: put the spacer kernel in front of a deferred side chain that forks on a RECORDED event
+        as well (an attached event always gets one).'''
         self.main = torch.cuda.current_stream(dev)
         n = min(nchains - 1, SIDE_STREAMS)
         self.sides = _side_streams(dev, n) if n > 0 else []
@@ -716,6 +789,7 @@ class _Fork(object):
         self.defer, self.keep = defer, keep
         self.lazy, self.forked = lazy, False
         self.event = event if (event is not None and event.attached) else None
+        self.spacer = spacer
 
     def _fork_now(self):
         if self.sides and not self.forked:
@@ -744,7 +818,7 @@ class _Fork(object):
             if q:
                 self.keep = tuple(self.keep) + tuple(k for _f, k in q)
                 _flush_lazy(s.device)  # queued small kernels ride on this fork's event
-            elif self.defer and self.event is not None and FORK_SPACER:
+            elif self.defer and (self.event is not None or self.spacer) and FORK_SPACER:
                 _spacer(s.device)
             return fn()
 
@@ -986,9 +1060,15 @@ BWD_DB = _lib.expert('lstm_bwd_db', True)
 DB_DEFER = _lib.expert('lstm_db_defer', True)
 
 
-def lstm_layer_bwd(c, dy, need_dx, layer_tag=None, is_top=False, ws_prefilled=None):
+def lstm_layer_bwd(c, dy, need_dx, layer_tag=None, is_top=False, ws_prefilled=None, dx_drop=None):
     '''dy: [T, B, ndir*H] contiguous.  Returns (dx [T*B, D] or None, dWs, dbs).
-    ws_prefilled: a workspace whose ring the caller prefilled (lstm_prefill_train)'''
+    ws_prefilled: a workspace whose ring the caller prefilled (lstm_prefill_train).
+    dx_drop: (DropoutSpec, stream_id) of the dropout that sits on this layer's INPUT (the output of
+    the BiLSTM layer below): dx is masked in place right behind the dX product, and the weight-
+    gradient side chain is forked behind THAT launch by a recorded event (+ the spacer) instead of
+    by the event attached to dX -- with the attached event the chain would become runnable one
+    mask launch before the next BPTT kernel and could take the CUs first ("who goes first",
+    DESIGN 3.1).'''
     T, B, H, D, ndir = c.T, c.B, c.H, c.D, c.ndir
     dev = dy.device
     das = [torch.empty(T * B, 4 * H, device=dev) for _ in range(ndir)]
@@ -1107,8 +1187,13 @@ def lstm_layer_bwd(c, dy, need_dx, layer_tag=None, is_top=False, ws_prefilled=No
     # the next layer's latency-bound BPTT kernel instead; the caller joins them
     # (`join_deferred`).
     fork_early = DW_FORK_EARLY and need_dx and GROUPED_DW
+    def drop_dx():
+        dropout_apply(dx, dx, T * B, D, D, D, dx_drop[0], dx_drop[1])
+
     if need_dx and not fork_early:
-        input_grad(attach=GROUPED_DW and overlap)
+        input_grad(attach=GROUPED_DW and overlap and dx_drop is None)
+        if dx_drop is not None:
+            drop_dx()
     hooks = bool(GRAD_READY_HOOKS) and _fast() and layer_tag is not None and \
         all(a and b for a, b in direct)
     if hooks and not need_dx:
@@ -1123,7 +1208,7 @@ def lstm_layer_bwd(c, dy, need_dx, layer_tag=None, is_top=False, ws_prefilled=No
         with torch.cuda.stream(sides[0]):
             _fire_grad_ready(('rest',), list(c.Ws) + list(c.bs))
     with _Fork(dev, ndir + 1, defer=True, keep=(das, c.x, c.ypad, dy, ws), lazy=True,
-               event=fork_ev[0]) as f:
+               event=fork_ev[0], spacer=dx_drop is not None) as f:
         on_main = False
         if GROUPED_DW and not need_dx:
             # bottom layer: no BPTT kernel follows, so the group takes the whole GPU on
@@ -1139,6 +1224,8 @@ def lstm_layer_bwd(c, dy, need_dx, layer_tag=None, is_top=False, ws_prefilled=No
             f.run(1, weight_grads_grouped)
             if fork_early:
                 input_grad()          # beside the group, both behind this layer's BPTT kernel
+                if dx_drop is not None:
+                    drop_dx()
         else:
             for d in range(ndir):
                 f.run(d + 1, lambda d=d: weight_grads(d))
@@ -1153,7 +1240,9 @@ def lstm_layer_bwd(c, dy, need_dx, layer_tag=None, is_top=False, ws_prefilled=No
 
 class LstmLayerFn(torch.autograd.Function):
     '''One (bi)LSTM layer on batch-major input: Model.lyr_lstm / _lyr_bilstm
-    (main.py:76-132, app/modules.py:120-137).  x [B,T,D] -> [B,T,ndir*H]'''
+    (main.py:76-132, app/modules.py:120-137).  x [B,T,D] -> [B,T,ndir*H].
+    Inside an active `dropout_scope` a bidirectional layer's output is dropped (app/modules.py:137);
+    a single direction (Model.lyr_lstm) has no dropout in the reference and none here.'''
 
     @staticmethod
     def forward(ctx, x, H, *params):
@@ -1164,12 +1253,23 @@ class LstmLayerFn(torch.autograd.Function):
         c = lstm_layer_fwd(xt, D, D, T, B, H, Ws, bs)
         ctx.c = c
         ctx.xt = xt
+        spec = _dropout_cur[0] if ndir == 2 else None
+        ctx.drop = None
+        if spec is not None:                        # tf.nn.dropout, app/modules.py:137
+            ctx.drop = (spec, spec.take())
+            yd = torch.empty(T, B, 2 * H, device=x.device)
+            dropout_apply(c.ypad[1:], yd, T * B, 2 * H, 2 * H, 2 * H, *ctx.drop)
+            return yd.transpose(0, 1).contiguous()
         return c.ypad[1:T + 1].transpose(0, 1).contiguous()
 
     @staticmethod
     def backward(ctx, dy):
         c = ctx.c
         dyt = dy.transpose(0, 1).contiguous()
+        if ctx.drop is not None:
+            # (out of place: .contiguous() may have handed back the caller's own tensor)
+            W = c.ndir * c.H
+            dyt = dropout_apply(dyt, torch.empty(c.T, c.B, W, device=dy.device), c.T * c.B, W, W, W, *ctx.drop)
         dx, dWs, dbs = lstm_layer_bwd(c, dyt, ctx.needs_input_grad[0])
         join_deferred()
         out = [None, None]
@@ -1184,7 +1284,13 @@ class RnnEncoderFn(torch.autograd.Function):
     '''Whole `bilstm-orig` / `lstm-orig` encoder (app/modules.py:148-260):
     mean-centre -> L stacked (bi)LSTM layers -> mean-centre -> bias-free output
     projection.  x [B,T,F] -> embed [B,T,F*E].
-    params = (W_0f, b_0f, [W_0b, b_0b], W_1f, ..., W_out)'''
+    params = (W_0f, b_0f, [W_0b, b_0b], W_1f, ..., W_out)
+    Inside an active `dropout_scope`, `bilstm-orig` (ndir == 2) drops every layer's output the way
+    `_lyr_bilstm` does (app/modules.py:137): the dropped copy of ypad[1:] goes to a buffer of its own,
+    which is the next layer's input (and its dWx operand) or the centring's; ypad stays intact as
+    the recurrent exchange medium and dWh operand.  Stream id = layer index.  `lstm-orig`
+    (ndir == 1) calls model.lyr_lstm directly in the reference (app/modules.py:164-179), which has
+    no dropout: it stays as it is.'''
 
     @staticmethod
     def forward(ctx, x, H, L, ndir, *params):
@@ -1213,6 +1319,8 @@ class RnnEncoderFn(torch.autograd.Function):
             if not encoder_prologue(x, B, T, F, xc, Fp, H, ndir, ypads, wss, bwss):
                 bwss = None
         ctx.bwss = bwss
+        spec = _dropout_cur[0] if ndir == 2 else None
+        ctx.drop = (spec, spec.take(L)) if spec is not None else None
         for l in range(L):                                    # modules.py:223-242
             Ws = [params[(l * ndir + d) * 2] for d in range(ndir)]
             bs = [params[(l * ndir + d) * 2 + 1] for d in range(ndir)]
@@ -1222,6 +1330,9 @@ class RnnEncoderFn(torch.autograd.Function):
                                ws=wss[l])
             ctxs.append(c)
             cur, ld, D = c.ypad[1:], ndir * H, ndir * H
+            if spec is not None:                              # modules.py:137
+                cur = dropout_apply(cur, torch.empty(T, B, D, device=dev), T * B, D, D, D, spec,
+                                    ctx.drop[1] + l)
         # y - mean_{t,h}(y), back to batch-major                modules.py:244-245
         yc = torch.empty(B, T, D, device=dev)
         center(cur, B, T, D, 1, D, yc, 0, D)
@@ -1267,13 +1378,18 @@ class RnnEncoderFn(torch.autograd.Function):
                 f.after_all(lambda: _fire_grad_ready(('out',), [ctx.Wout]))
         dy = torch.empty(T, B, D, device=dev)
         center(dyc, B, T, D, 0, D, dy, 1, D)                 # centre is self-adjoint
+        drop = ctx.drop
+        if drop is not None:                                 # the top layer's mask (dy is ours: in place)
+            dropout_apply(dy, dy, T * B, D, D, D, drop[0], drop[1] + L - 1)
         grads = [None] * (2 * L * ndir)
         # partial-dh rings of all layers' BPTT launches: prefilled by the forward pass's fill launch
         bwss = ctx.bwss if ctx.bwss is not None else [None] * L
         ctx.bwss = None
         for l in reversed(range(L)):
             dx, dWs, dbs = lstm_layer_bwd(ctx.ctxs[l], dy, need_dx=(l > 0), layer_tag=l,
-                                          is_top=(l == L - 1), ws_prefilled=bwss[l])
+                                          is_top=(l == L - 1), ws_prefilled=bwss[l],
+                                          dx_drop=(drop[0], drop[1] + l - 1) if (drop is not None and l > 0)
+                                          else None)
             for d in range(ndir):
                 grads[(l * ndir + d) * 2] = dWs[d]
                 grads[(l * ndir + d) * 2 + 1] = dbs[d]
@@ -1376,7 +1492,8 @@ class ConvBiLstmEncoderFn(torch.autograd.Function):
     each other their layouts through strides (conv_encoder_descs), so there are no copies.
     params = (w0, b0, .., w3, b3, W_0f, b_0f, W_0b, b_0b, W_1f, b_1f, W_1b, b_1b, w4, b4, .., w7, b7,
     W_dense).  debug: None or a dict that receives conv_act, lstm_act (time-major [T/4][B][2 nfft])
-    and mid4 ([B][16][T/2][nfft/4]).'''
+    and mid4 ([B][16][T/2][nfft/4]).  Inside an active `dropout_scope` both BiLSTM layers drop their
+    outputs as in RnnEncoderFn; the residual add sees the dropped lstm1 output.'''
 
     @staticmethod
     def forward(ctx, x, nfft, alpha, debug, *params):
@@ -1412,9 +1529,17 @@ class ConvBiLstmEncoderFn(torch.autograd.Function):
         center(p3, B, T4, D, 1, D, conv_act, 1, D)                                       # :313
         c0 = lstm_layer_fwd(conv_act, D, D, T4, B, H, list(lp[0:4:2]), list(lp[1:4:2]),  # :315-324
                             ypad=ypads[0], ws=wss[0])
-        c1 = lstm_layer_fwd(c0.ypad[1:], D, D, T4, B, H, list(lp[4:8:2]), list(lp[5:8:2]),  # :325-329
+        spec = _dropout_cur[0]
+        ctx.drop = (spec, spec.take(2)) if spec is not None else None
+        y0 = c0.ypad[1:]
+        if spec is not None:                         # _lyr_bilstm's dropout (modules.py:137), stream id = layer
+            y0 = dropout_apply(y0, torch.empty(T4, B, D, device=dev), T4 * B, D, D, D, spec, ctx.drop[1])
+        c1 = lstm_layer_fwd(y0, D, D, T4, B, H, list(lp[4:8:2]), list(lp[5:8:2]),           # :325-329
                             ypad=ypads[1], ws=wss[1])
-        s = conv_add(c1.ypad[1:T4 + 1], conv_act, torch.empty(T4, B, D, device=dev))     # :333
+        y1 = c1.ypad[1:T4 + 1]
+        if spec is not None:                         # the residual add sees the dropped lstm1 output
+            y1 = dropout_apply(y1, torch.empty(T4, B, D, device=dev), T4 * B, D, D, D, spec, ctx.drop[1] + 1)
+        s = conv_add(y1, conv_act, torch.empty(T4, B, D, device=dev))                    # :333
         lstm_act = torch.empty(T4, B, D, device=dev)
         center(s, B, T4, D, 1, D, lstm_act, 1, D)                                        # :334
         a4 = conv_fwd(ds[4], lstm_act, *cw[4], torch.empty(B, 32, T4, N8, device=dev))   # :339-343
@@ -1479,8 +1604,12 @@ class ConvBiLstmEncoderFn(torch.autograd.Function):
         ctx.bwss = None
         c0, c1 = ctx.lstm
         dy = g
+        drop = ctx.drop
+        if drop is not None:       # lstm1's mask; out of place: the residual branch keeps the unmasked g
+            dy = dropout_apply(g, torch.empty(T4, B, D, device=dev), T4 * B, D, D, D, drop[0], drop[1] + 1)
         for l, c in ((1, c1), (0, c0)):
-            dx, dWs, dbs = lstm_layer_bwd(c, dy, need_dx=True, is_top=(l == 1), ws_prefilled=bwss[l])
+            dx, dWs, dbs = lstm_layer_bwd(c, dy, need_dx=True, is_top=(l == 1), ws_prefilled=bwss[l],
+                                          dx_drop=(drop[0], drop[1]) if (drop is not None and l == 1) else None)
             for d in range(2):
                 grads[8 + 4 * l + 2 * d], grads[9 + 4 * l + 2 * d] = dWs[d], dbs[d]
             dy = dx
