@@ -7,8 +7,9 @@ One object per .hip/.cpp under csrc/, compiled in parallel, linked into
 csrc/libdanet_hip.so.  The extension library of the conv-bilstm-v1 encoder
 (csrc/conv/*.hip -> csrc/libdanet_conv_hip.so, include/danet_conv_hip.h) is
 built by the same call, and so is the dropout extension (csrc/dropout/*.hip ->
-csrc/libdanet_dropout_hip.so, include/danet_dropout_hip.h).  Objects are rebuilt only when their source (or a shared
-header) is newer.  No torch headers are involved: the library is a plain C ABI
+csrc/libdanet_dropout_hip.so, include/danet_dropout_hip.h) and the dataset front-end extension
+(csrc/prep/*.hip -> csrc/libdanet_prep_hip.so, include/danet_prep_hip.h).  Objects are rebuilt only when their
+source (or a shared header) is newer.  No torch headers are involved: the library is a plain C ABI
 (include/danet_hip.h).
 '''
 import os
@@ -27,6 +28,9 @@ CONV_LIB = os.path.join(CSRC, 'libdanet_conv_hip.so')
 DROPOUT_CSRC = os.path.join(CSRC, 'dropout')
 DROPOUT_BUILD = os.path.join(DROPOUT_CSRC, 'build')
 DROPOUT_LIB = os.path.join(CSRC, 'libdanet_dropout_hip.so')
+PREP_CSRC = os.path.join(CSRC, 'prep')
+PREP_BUILD = os.path.join(PREP_CSRC, 'build')
+PREP_LIB = os.path.join(CSRC, 'libdanet_prep_hip.so')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # -fvisibility=hidden: only what include/danet_hip.h declares (inside its visibility pragma) is exported
@@ -87,6 +91,7 @@ def build(force=False, verbose=True):
             LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
     build_conv(force=force, verbose=verbose)
     build_dropout(force=force, verbose=verbose)
+    build_prep(force=force, verbose=verbose)
     return LIB
 
 
@@ -122,6 +127,22 @@ def build_dropout(force=False, verbose=True):
         print('libdanet_dropout_hip.so: %s (%d objects, %s)' % (
             DROPOUT_LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
     return DROPOUT_LIB
+
+
+def build_prep(force=False, verbose=True):
+    '''csrc/prep/*.hip -> csrc/libdanet_prep_hip.so (objects under csrc/prep/build/)'''
+    os.makedirs(PREP_BUILD, exist_ok=True)
+    hdr_m = os.path.getmtime(os.path.join(INCLUDE, 'danet_prep_hip.h'))
+    srcs = sorted(f for f in os.listdir(PREP_CSRC) if f.endswith('.hip'))
+    res = [_compile(s, force, hdr_m, PREP_BUILD, src_dir=PREP_CSRC) for s in srcs]
+    objs = [o for o, _ in res]
+    rebuilt = any(r for _, r in res)
+    if rebuilt or not os.path.exists(PREP_LIB):
+        _link(objs, PREP_LIB, exports=os.path.join(PREP_CSRC, 'exports.map'))
+    if verbose:
+        print('libdanet_prep_hip.so: %s (%d objects, %s)' % (
+            PREP_LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
+    return PREP_LIB
 
 
 def build_variant(name, defs):

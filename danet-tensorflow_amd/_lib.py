@@ -263,6 +263,54 @@ def dropout_check(rc):
         raise DanetHipError('libdanet_dropout_hip error %d: %s' % (rc, msg.decode() if msg else '?'))
 
 
+# ---- the dataset front-end extension library (include/danet_prep_hip.h) ----
+# Loaded at the first use of the `wavdir` dataset (ops.stft_batch) only: a run with any other
+# DATASET_TYPE never maps it.
+PREP_LIB_PATH = os.path.join(_HERE, 'csrc', 'libdanet_prep_hip.so')
+PREP_ABI_VERSION = 1
+# name -> (restype, argtypes); mirrors include/danet_prep_hip.h
+PREP_PROTOTYPES = {
+    'danet_prep_abi_version': (c_int, []),
+    'danet_prep_last_error': (ctypes.c_char_p, []),
+    'danet_prep_num_frames': (c_int, [c_i64, c_int, c_int]),
+    'danet_prep_workspace_bytes': (c_sz, [c_int]),
+    'danet_prep_stft_plan': (c_int, [c_p, c_int, c_p, c_p, c_sz]),
+    'danet_prep_stft_batch': (c_int, [c_p, c_int, c_p, c_i64, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p,
+                                      c_p, c_i64]),
+}
+_prep = None
+
+
+def load_prep():
+    '''dlopen libdanet_prep_hip.so (after torch)'''
+    global _prep
+    if _prep is not None:
+        return _prep
+    with _lock:
+        if _prep is not None:
+            return _prep
+        if not os.path.exists(PREP_LIB_PATH):
+            raise DanetHipError(
+                'libdanet_prep_hip.so not found at %s -- the wavdir dataset needs the HIP '
+                'extension library (there is no CPU fallback); build it with '
+                '`python -c "import __graft_entry__ as g; g.build()"`' % PREP_LIB_PATH)
+        lib = ctypes.CDLL(PREP_LIB_PATH, mode=ctypes.RTLD_LOCAL)
+        for name, (res, args) in PREP_PROTOTYPES.items():
+            fn = getattr(lib, name)      # AttributeError if the symbol is missing
+            fn.restype = res
+            fn.argtypes = args
+        if lib.danet_prep_abi_version() != PREP_ABI_VERSION:
+            raise DanetHipError('libdanet_prep_hip.so ABI version mismatch')
+        _prep = lib
+    return _prep
+
+
+def prep_check(rc):
+    if rc != 0:
+        msg = load_prep().danet_prep_last_error()
+        raise DanetHipError('libdanet_prep_hip error %d: %s' % (rc, msg.decode() if msg else '?'))
+
+
 # ---- switches ------------------------------------------------------------------
 # USER switches (README): DANET_GEMM_X6, DANET_LSTM_FWD_FUSED, DANET_SIDE_STREAMS, DANET_FEED_MODE,
 # DANET_OVERLAP_ALLREDUCE, DANET_ALLREDUCE_TAIL_RATIO, DANET_MAX_STEPS_IN_FLIGHT, DANET_STATUS_HOST, DANET_FUSE_HEADS,

@@ -43,7 +43,9 @@ def train_epoch(model, batches, out=sys.stdout, sync_feed=None):
     MAX_TRAIN_LEN (main.py:422-426), one train step per batch, a ':' per step, epoch means of the
     fetched metrics.  The host never waits for the device inside the loop: batches are staged,
     cropped and uploaded one step ahead (feed.BatchFeed), the per-step metrics stay on the device
-    until the epoch mean is read (feed.StepReport).  sync_feed=True is the reference's literal
+    until the epoch mean is read (feed.StepReport).  `batches` may also be a feed.EpochSource: a dataset
+    that builds its batches on the device (wavdir) is then asked for them directly (feed.open_feed)
+    instead of going through BatchFeed.  sync_feed=True is the reference's literal
     form -- blocking upload, `float()` of every metric every step -- kept for the equality test
     and `bench.py --e2e --sync-feed`.  Returns (OrderedDict of epoch means, number of batches).
     LIFETIME of a batch tensor in the 'ahead' mode: it is a view of one of three reused device
@@ -52,8 +54,7 @@ def train_epoch(model, batches, out=sys.stdout, sync_feed=None):
     be cloned by the caller; Model.train_step itself keeps nothing.'''
     if sync_feed is None:
         sync_feed = SYNC_FEED
-    src = feed.BatchFeed(batches, model.device, hparams.MAX_TRAIN_LEN,
-                         mode='sync' if sync_feed else None)
+    src = feed.open_feed(batches, model.device, hparams.MAX_TRAIN_LEN, sync_feed)
     report = feed.StepReport(flush_every=1 if sync_feed else 1024)
     for spectra in src:
         step_fetch = model.train_step(spectra)
@@ -71,8 +72,8 @@ def train(model, n_epoch, dataset, args, out=sys.stdout):
     out.write('Set learning rate to %f\n' % hparams.LR)
     i_epoch = 0
     while i_epoch < n_epoch:
-        cli_report, _n = train_epoch(model, dataset.epoch(
-            'train', hparams.BATCH_SIZE * hparams.MAX_N_SIGNAL, shuffle=True), out,
+        cli_report, _n = train_epoch(model, feed.EpochSource(
+            dataset, 'train', hparams.BATCH_SIZE * hparams.MAX_N_SIGNAL, shuffle=True), out,
             sync_feed=getattr(args, 'sync_feed', None))
         model.check_status()       # hand-off timeouts of the persistent kernels surface here at the latest
         # data parallel: every rank must take the SAME learning-rate and NaN decisions, so
@@ -142,9 +143,8 @@ def evaluate(model, dataset, subset, out=sys.stdout, sync_feed=None):
     train_epoch (no crop: main.py:497-498)'''
     if sync_feed is None:
         sync_feed = SYNC_FEED
-    src = feed.BatchFeed(dataset.epoch(subset, hparams.BATCH_SIZE * hparams.MAX_N_SIGNAL,
-                                       shuffle=False), model.device, None,
-                         mode='sync' if sync_feed else None)
+    src = feed.open_feed(feed.EpochSource(dataset, subset, hparams.BATCH_SIZE * hparams.MAX_N_SIGNAL,
+                                          shuffle=False), model.device, None, sync_feed)
     report = feed.StepReport(flush_every=1 if sync_feed else 1024)
     for spectra in src:
         report.add(model.valid_step(spectra))

@@ -2,8 +2,14 @@
 Datasets.  Only the reference's data-free `toy` generator
 (app/datasets/dataset.py:43-63) is re-stated; `timit` / `wsj0` need licensed
 corpora and are out of scope.  `synth` is the speech-shaped 8 kHz
-2-speaker generator the benchmarks use.
+2-speaker generator the benchmarks use.  `wavdir` trains on a folder of the user's
+own WAV files: waveforms resident in device memory, every batch one launch of the ragged-batch
+STFT kernel (include/danet_prep_hip.h).
 '''
+import os
+import random
+from math import ceil
+
 import numpy as np
 
 from .hparams import hparams
@@ -15,6 +21,11 @@ class Dataset(object):
         self.is_loaded = False
 
     def epoch(self, subset, batch_size, shuffle=False):
+        '''yields (numpy batch [batch_size, T, F],) per batch.  Two OPTIONAL, independent extensions, both
+        looked up by cli through feed.EpochSource: an epoch() that computes its batches on a GPU may take a
+        further keyword `device=None` (it is then handed the model's device); a dataset that can build
+        the cropped batch on the device offers
+        `epoch_device(subset, batch_size, shuffle=False, device=None, crop_len=None)`.'''
         raise NotImplementedError()
 
     def install_and_load(self):
@@ -116,3 +127,230 @@ class SynthVarLenSpeechData(SynthSpeechData):
             max_len = max(map(len, data))
             spectra_li = [utils.random_zeropad(x, max_len - len(x), axis=-2) for x in data]
             yield (np.stack(spectra_li),)
+
+
+def _stft_frames(n_samples, fft_size, fft_stride):
+    '''frames of scipy.signal.stft(boundary='zeros', padded=True) = danet_prep_num_frames'''
+    nadd = (-n_samples % fft_stride) % fft_size
+    return (n_samples + nadd) // fft_stride + 1
+
+
+class _DescSlot(object):
+    '''one pinned descriptor table + its device copy + the event behind the last upload out of it'''
+    __slots__ = ('pin', 'dev', 'event', 'used')
+
+
+@hparams.register_dataset('wavdir')
+class WavDirData(Dataset):
+    '''a folder of single-channel WAV files: hparams.DATASET_DIR/{train,valid,test}/**/*.wav, taken in
+    sorted path order (a missing `valid` folder falls back to `test`, as app/datasets/timit.py:111-113).
+
+    Files are decoded once (scipy.io.wavfile, float32 at their STORED scale: the reference feeds
+    un-normalised int16-scale waveforms), resampled to SMPRATE exactly as utils.load_wavfile does, and
+    kept as ONE float32 pool per subset that is uploaded to the device once.  Files shorter than
+    FFT_SIZE samples after resampling are skipped and counted.
+
+    Batching is the reference's (app/datasets/wsj0.py:40-56): indices arange(ceil(n/bs)*bs) % n,
+    np.random.shuffle when `shuffle`; per batch every spectrogram is zero-padded on both sides of the
+    time axis to the longest of the batch, the left pad drawn as utils.random_zeropad draws it.  The
+    padded batch is not built on the host: ops.stft_batch writes it in one launch.
+
+    epoch()         the host-literal form every dataset has: numpy complex64 [batch, T_max, F]
+    epoch_device()  the fast form: device tensors [B, C, T', F], crop included, no host copy'''
+    SUBSETS = ('train', 'valid', 'test')
+    DESC_DEPTH = 8        # pinned descriptor tables in flight
+    OUT_DEPTH = 3         # output buffers: a yielded batch stays valid while the next two are drawn
+
+    def __init__(self):
+        Dataset.__init__(self)
+        self.files, self.lengths, self.offsets, self.frames = {}, {}, {}, {}
+        self.pool_host, self.skipped = {}, {}
+        self._pool_dev, self._window, self._ring = {}, {}, {}
+
+    # ---- host half -------------------------------------------------------------------------------
+    @staticmethod
+    def read_wave(filename):
+        '''WAV -> float32 waveform at SMPRATE (utils.load_wavfile up to the STFT)'''
+        import scipy.io.wavfile
+        import scipy.signal
+        smprate, data = scipy.io.wavfile.read(filename)
+        if data.ndim != 1:
+            raise ValueError('%s has %d channels; the wavdir dataset takes single-channel files'
+                             % (filename, data.shape[1]))
+        if smprate != hparams.SMPRATE:
+            data = scipy.signal.resample(data, int(ceil(len(data) * hparams.SMPRATE / smprate)))
+        return np.asarray(data, dtype=np.float32)
+
+    @staticmethod
+    def discover(folder):
+        '''every *.wav below `folder`, sorted by path'''
+        found = []
+        for base, _dirs, names in os.walk(folder):
+            found += [os.path.join(base, n) for n in names if n.lower().endswith('.wav')]
+        return sorted(found)
+
+    def load_host(self, out=None):
+        '''discover, decode and resample every subset into host pools (no device involved)'''
+        root = hparams.DATASET_DIR
+        if root is None:
+            raise ValueError('the wavdir dataset needs hparams.DATASET_DIR: the folder that holds '
+                             'train/, test/ and optionally valid/')
+        for subset in self.SUBSETS:
+            folder = os.path.join(root, subset)
+            if not os.path.isdir(folder):
+                if subset == 'valid':
+                    continue
+                raise IOError('wavdir: folder %s not found' % folder)
+            files, waves, skipped = [], [], 0
+            for fn in self.discover(folder):
+                w = self.read_wave(fn)
+                if len(w) < hparams.FFT_SIZE:
+                    skipped += 1
+                    continue
+                files.append(fn)
+                waves.append(w)
+            print('wavdir %s: %d files, %d shorter than FFT_SIZE skipped' % (subset, len(files), skipped),
+                  file=out)
+            if not files:
+                raise IOError('wavdir: no usable WAV file under %s' % folder)
+            lens = np.asarray([len(w) for w in waves], dtype=np.int64)
+            self.files[subset], self.lengths[subset], self.skipped[subset] = files, lens, skipped
+            self.offsets[subset] = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+            self.frames[subset] = np.asarray(
+                [_stft_frames(int(n), hparams.FFT_SIZE, hparams.FFT_STRIDE) for n in lens], dtype=np.int64)
+            self.pool_host[subset] = np.concatenate(waves)
+        self._alias = 'valid' not in self.files
+        if self._alias:                   # app/datasets/timit.py:111-113
+            for table in (self.files, self.lengths, self.offsets, self.frames, self.pool_host, self.skipped):
+                table['valid'] = table['test']
+
+    def install_and_load(self):
+        self.load_host()
+        self.is_loaded = True
+
+    # ---- the batching plan (host, no device) -------------------------------------------------------
+    def plan_indices(self, subset, batch_size, shuffle=False):
+        '''[n_batch, batch_size] utterance indices of one epoch (app/datasets/wsj0.py:42-47)'''
+        n = len(self.lengths[subset])
+        indices = np.arange(((n + batch_size - 1) // batch_size) * batch_size)
+        indices %= n
+        if shuffle:
+            np.random.shuffle(indices)
+        return indices.reshape(-1, batch_size)
+
+    def plan_batch(self, subset, idx, crop_len=None, crop=False):
+        '''(T_max, pad_left per utterance, t_begin, t_count) of one batch; draws from python's `random`
+        exactly as utils.random_zeropad does per utterance (no draw for a full-length one) and then,
+        with crop=True, as feed.to_batch_host does for the crop'''
+        T = self.frames[subset][idx]
+        T_max = int(T.max())
+        pads = [random.randint(0, T_max - int(t)) if T_max > int(t) else 0 for t in T]
+        beg, cnt = 0, T_max
+        if crop and crop_len is not None and T_max > crop_len:
+            beg = random.randint(0, T_max - crop_len - 1)                 # main.py:424-425
+            cnt = crop_len
+        return T_max, pads, beg, cnt
+
+    # ---- device half -----------------------------------------------------------------------------
+    @staticmethod
+    def _device(device=None):
+        import torch
+        device = torch.device('cuda' if device is None else device)
+        if device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        return device
+
+    def upload_pool(self, subset, device):
+        '''the subset's float32 pool on `device` (uploaded once)'''
+        import torch
+        key = ('test' if (subset == 'valid' and self._alias) else subset, str(device))
+        pool = self._pool_dev.get(key)
+        if pool is None:
+            pool = self._pool_dev[key] = torch.from_numpy(self.pool_host[subset]).to(device)
+        return pool
+
+    def _window_on(self, device):
+        import torch
+        w = self._window.get(str(device))
+        if w is None:
+            w = self._window[str(device)] = torch.as_tensor(
+                np.asarray(hparams.FFT_WND, dtype=np.float32)).to(device)
+        return w
+
+    def epoch(self, subset, batch_size, shuffle=False, device=None):
+        '''numpy complex64 [batch_size, T_max, F] per batch.  The spectra are computed on `device` (default:
+        the current CUDA device; cli passes the model's, so the pool is uploaded once, where the model is)'''
+        if not self.is_loaded:
+            raise RuntimeError('Dataset is not loaded.')
+        from . import ops
+        device = self._device(device)
+        pool, window = self.upload_pool(subset, device), self._window_on(device)
+        for idx in self.plan_indices(subset, batch_size, shuffle):
+            T_max, pads, _beg, _cnt = self.plan_batch(subset, idx)
+            desc = ops.prep_desc(self.offsets[subset][idx], self.lengths[subset][idx], pads, T_max,
+                                 pool.numel(), hparams.FFT_SIZE, hparams.FFT_STRIDE)
+            spectra = ops.stft_batch(pool, desc, T_max, window, hparams.FFT_SIZE, hparams.FFT_STRIDE,
+                                     t_begin=0, t_count=T_max)
+            yield (spectra.cpu().numpy(),)
+
+    def _take_ring(self, device, n_utt):
+        import torch
+        ring = self._ring.get(str(device))
+        if ring is None or ring['n_utt'] < n_utt:
+            from . import ops
+            slots = []
+            for _ in range(self.DESC_DEPTH):
+                s = _DescSlot()
+                s.pin = torch.zeros(n_utt * ops.PREP_DESC_DTYPE.itemsize, dtype=torch.uint8).pin_memory()
+                s.dev = torch.zeros(n_utt * ops.PREP_DESC_DTYPE.itemsize, dtype=torch.uint8, device=device)
+                s.event, s.used = torch.cuda.Event(), False
+                slots.append(s)
+            ring = self._ring[str(device)] = dict(n_utt=n_utt, slots=slots, out=[None] * self.OUT_DEPTH, k=0)
+        return ring
+
+    def epoch_device(self, subset, batch_size, shuffle=False, device=None, crop_len=None):
+        '''the batches of epoch() -- same index plan, same pad draws -- followed by the crop draw of
+        feed.to_batch_host, as complex64 DEVICE tensors [BATCH_SIZE, MAX_N_SIGNAL, T', F]: one
+        ops.stft_batch launch per batch computes only the cropped frames; per batch a 24-byte row per
+        utterance crosses PCIe, from a pinned ring, without a host wait.  Everything is enqueued on the
+        stream that is current in the consumer.  LIFETIME: a yielded tensor is a view of one of
+        OUT_DEPTH reused device buffers and stays valid until the consumer has asked for OUT_DEPTH - 1
+        more batches (the same rule as feed.BatchFeed; clone it to keep it longer).'''
+        if not self.is_loaded:
+            raise RuntimeError('Dataset is not loaded.')
+        device = self._device(device)
+        F, B, C = hparams.FEATURE_SIZE, hparams.BATCH_SIZE, hparams.MAX_N_SIGNAL
+        assert batch_size == B * C, (batch_size, B, C)
+        pool, window = self.upload_pool(subset, device), self._window_on(device)
+        ring = self._take_ring(device, batch_size)
+        for idx in self.plan_indices(subset, batch_size, shuffle):
+            T_max, pads, beg, cnt = self.plan_batch(subset, idx, crop_len, crop=True)
+            out = self._emit(device, pool, window, ring, subset, idx, T_max, pads, beg, cnt)
+            yield out.view(B, C, cnt, F)
+
+    def _emit(self, device, pool, window, ring, subset, idx, T_max, pads, beg, cnt):
+        '''the device half of one batch: descriptor table through the pinned ring, one launch into the
+        next output buffer -> complex64 [batch, cnt, F]'''
+        import torch
+        from . import ops
+        N, S, F = hparams.FFT_SIZE, hparams.FFT_STRIDE, hparams.FEATURE_SIZE
+        batch_size, row = len(idx), ops.PREP_DESC_DTYPE.itemsize
+        k = ring['k']
+        ring['k'] = k + 1
+        slot = ring['slots'][k % self.DESC_DEPTH]
+        if slot.used:
+            slot.event.synchronize()      # the copy out of this table DESC_DEPTH batches ago: long done
+        table = slot.pin[:batch_size * row].numpy().view(ops.PREP_DESC_DTYPE)
+        ops.prep_desc(self.offsets[subset][idx], self.lengths[subset][idx], pads, T_max,
+                      pool.numel(), N, S, out=table)
+        dev_table = slot.dev[:batch_size * row]
+        dev_table.copy_(slot.pin[:batch_size * row], non_blocking=True)
+        slot.event.record(torch.cuda.current_stream(device))
+        slot.used = True
+        n = batch_size * cnt * F
+        buf = ring['out'][k % self.OUT_DEPTH]
+        if buf is None or buf.numel() < n:
+            buf = ring['out'][k % self.OUT_DEPTH] = torch.empty(n, dtype=torch.complex64, device=device)
+        out = buf[:n].view(batch_size, cnt, F)
+        ops.stft_batch(pool, dev_table, T_max, window, N, S, t_begin=beg, t_count=cnt, out=out)
+        return out

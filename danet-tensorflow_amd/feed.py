@@ -26,6 +26,7 @@ shares a queue with the main or the side stream and the step is 1 ms slower -- t
 the existing side stream, which is idle during the forward pass); device buffers from the caching
 allocator (`record_stream`: re-allocation and event polling every step).
 '''
+import inspect
 from random import randint
 
 import numpy as np
@@ -199,6 +200,44 @@ class BatchFeed(object):
         finally:
             self._consumed()                      # (a consumer that left the loop early: its last
             self._ent['busy'] = False             # batch's buffer is protected all the same)
+
+
+class EpochSource(object):
+    '''one epoch of one subset of a dataset, as cli hands it to train_epoch / evaluate: iterating it
+    is `dataset.epoch(...)` (host batches, for BatchFeed); a dataset that builds its batches on the
+    device (`epoch_device`, the wavdir dataset) is asked for them directly by open_feed().'''
+
+    def __init__(self, dataset, subset, batch_size, shuffle=False):
+        self.dataset, self.subset, self.batch_size, self.shuffle = dataset, subset, batch_size, shuffle
+        self.device = None        # set by open_feed: where a device-side dataset computes its host batches too
+
+    def __iter__(self):
+        # (a dataset says that its epoch() computes on a device by taking a `device` keyword: datasets.Dataset)
+        if self.device is not None and 'device' in inspect.signature(self.dataset.epoch).parameters:
+            return iter(self.dataset.epoch(self.subset, self.batch_size, shuffle=self.shuffle,
+                                           device=self.device))
+        return iter(self.dataset.epoch(self.subset, self.batch_size, shuffle=self.shuffle))
+
+    def device_batches(self, device, crop_len=None):
+        '''the dataset's own device-side batches, or None when it has no such route'''
+        fn = getattr(self.dataset, 'epoch_device', None)
+        if fn is None:
+            return None
+        return fn(self.subset, self.batch_size, shuffle=self.shuffle, device=device, crop_len=crop_len)
+
+
+def open_feed(source, device, crop_len=None, sync_feed=False):
+    '''the iterator of device batches [B, C, T', F] behind train_epoch / evaluate: the dataset's
+    device-side route when `source` is an EpochSource of a dataset that offers one and the feed is not
+    the synchronous one; BatchFeed over the host batches otherwise (every other dataset, plain
+    iterators, sync_feed)'''
+    if isinstance(source, EpochSource):
+        it = source.device_batches(device, crop_len) if not sync_feed else None
+        if it is not None:
+            return it
+        if torch.device(device).type == 'cuda':
+            source.device = device
+    return BatchFeed(source, device, crop_len, mode='sync' if sync_feed else None)
 
 
 class StepReport(object):

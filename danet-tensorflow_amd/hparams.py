@@ -17,6 +17,7 @@ unchanged.  Differences, all deliberate:
   `Model.train_step` passes it on and the BiLSTM encoders apply
   `tf.nn.dropout` where `_lyr_bilstm` has it (`app/modules.py:137`).  The
   default 1.0 is exactly the reference's behaviour.
+* `DATASET_DIR` (default None) names the folder the `wavdir` dataset reads.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -65,6 +66,8 @@ DEFAULTS = {
     'LSTM_HDIM': 300,
     # k-means estimator (not in the reference, README.md:216; BASELINE cfg 5)
     'KMEANS_ITERS': 10,
+    # root folder of the `wavdir` dataset: DATASET_DIR/{train,valid,test}/**/*.wav (not in the reference)
+    'DATASET_DIR': None,
 }
 
 

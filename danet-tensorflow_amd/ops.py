@@ -12,6 +12,7 @@ import ctypes
 import itertools
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -377,6 +378,97 @@ def istft(X, stride, window):
     check(L.danet_istft(_lib.stream(), n_sig, T, N, stride, ptr(torch.view_as_real(X)),
                         ptr(_f32(window)), ptr(out), ptr(w), wn))
     return out[0] if squeeze else out
+
+
+# ---- ragged-batch STFT of the wavdir dataset (include/danet_prep_hip.h) ----------------------------
+# On the extension library libdanet_prep_hip.so, mapped at the first call.  ops.stft above stays the
+# front-end of every other path.
+PREP_DESC_DTYPE = np.dtype([('offset', '<i8'), ('length', '<i8'), ('pad_left', '<i4'), ('reserved', '<i4')])
+_prep_plans = {}         # (device index, N, window bytes) -> plan tensor
+_prep_plans_fast = {}    # (device index, N, window data_ptr, window version) -> (window, plan)
+
+
+def prep_num_frames(n_samples, fft_size, fft_stride):
+    '''frames of an n_samples waveform (danet_prep_num_frames); ValueError when it is shorter than the window'''
+    T = _lib.load_prep().danet_prep_num_frames(int(n_samples), fft_size, fft_stride)
+    if T < 0:
+        raise ValueError('window is longer than input signal')
+    return T
+
+
+def prep_desc(offsets, lengths, pad_left, T_out, pool_len, fft_size, fft_stride, out=None):
+    '''the validated descriptor table of one ragged batch as a numpy record array (PREP_DESC_DTYPE; into
+    `out` when given).  Everything the kernel would have to clamp is a ValueError HERE, before any
+    upload or launch: an utterance outside the pool, shorter than the window, or placed beyond T_out.'''
+    n = len(offsets)
+    d = np.zeros(n, PREP_DESC_DTYPE) if out is None else out
+    assert d.dtype == PREP_DESC_DTYPE and d.shape == (n,)
+    for u in range(n):
+        o, l, p = int(offsets[u]), int(lengths[u]), int(pad_left[u])
+        if o < 0 or l < 0 or o + l > pool_len:
+            raise ValueError('stft_batch: utterance %d [%d, %d) is outside the pool of %d samples' % (u, o, o + l, pool_len))
+        T_u = prep_num_frames(l, fft_size, fft_stride)
+        if p < 0 or p + T_u > T_out:
+            raise ValueError('stft_batch: utterance %d: pad_left %d + %d frames exceeds T_out = %d' % (u, p, T_u, T_out))
+        d[u] = (o, l, p, 0)
+    return d
+
+
+def _prep_plan(window, fft_size):
+    '''the (device, N, window) plan: twiddles + 1/sum(window), built once by danet_prep_stft_plan'''
+    dev = window.device.index if window.device.index is not None else torch.cuda.current_device()
+    fast = (dev, fft_size, window.data_ptr(), window._version)
+    hit = _prep_plans_fast.get(fast)
+    if hit is not None:
+        return hit[1]
+    key = (dev, fft_size, window.detach().cpu().numpy().tobytes())
+    plan = _prep_plans.get(key)
+    if plan is None:
+        L = _lib.load_prep()
+        nbytes = L.danet_prep_workspace_bytes(fft_size)
+        if nbytes == ctypes.c_size_t(-1).value:
+            _lib.prep_check(-1)
+        plan = torch.zeros(nbytes, dtype=torch.uint8, device=window.device)
+        _lib.prep_check(L.danet_prep_stft_plan(_lib.stream(), fft_size, ptr(window), ptr(plan), nbytes))
+        _prep_plans[key] = plan
+    if len(_prep_plans_fast) >= 64:
+        _prep_plans_fast.clear()
+    _prep_plans_fast[fast] = (window, plan)      # the reference keeps data_ptr from being reused
+    return plan
+
+
+def stft_batch(pool, desc, T_out, window, fft_size, fft_stride, t_begin=0, t_count=None, out=None):
+    '''frames [t_begin, t_begin + t_count) of the zero-padded batch of the utterances `desc` describes
+    -> complex64 [n_utt, t_count, F], ONE launch (danet_prep_stft_batch).
+    pool: float32 device vector of waveforms laid back to back.  desc: the table of ops.prep_desc --
+    a numpy record array (validated again and uploaded here) or a device uint8 / int64 tensor of 24-byte
+    rows the caller has validated and uploaded.  window: float32 device vector.  out: optional
+    complex64 [n_utt, t_count, >= F] view whose last dimension is contiguous (its row pitch is used).'''
+    assert pool.is_cuda and pool.dtype == torch.float32 and pool.dim() == 1 and pool.is_contiguous()
+    window = _f32(window)
+    assert window.device == pool.device and window.numel() == fft_size
+    if t_count is None:
+        t_count = T_out - t_begin
+    F = fft_size // 2 + 1
+    if not torch.is_tensor(desc):
+        desc = np.asarray(desc)
+        if desc.dtype != PREP_DESC_DTYPE:
+            raise TypeError('stft_batch: desc must be a PREP_DESC_DTYPE record array or a device tensor')
+        prep_desc(desc['offset'], desc['length'], desc['pad_left'], T_out, pool.numel(), fft_size, fft_stride)
+        desc = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8).copy()).to(pool.device)
+    assert desc.is_cuda and desc.is_contiguous() and (desc.numel() * desc.element_size()) % 24 == 0
+    n_utt = desc.numel() * desc.element_size() // 24
+    if out is None:
+        out = torch.empty(n_utt, t_count, F, dtype=torch.complex64, device=pool.device)
+    assert out.dtype == torch.complex64 and out.is_cuda and tuple(out.shape) == (n_utt, t_count, F), out.shape
+    ld = out.stride(1) if t_count > 1 else max(out.stride(1), F)
+    assert out.stride(2) == 1 and (n_utt == 1 or out.stride(0) == t_count * ld), out.stride()
+    plan = _prep_plan(window, fft_size)
+    with _lib.timed('stft_batch'):
+        _lib.prep_check(_lib.load_prep().danet_prep_stft_batch(
+            _lib.stream(), n_utt, ptr(pool), pool.numel(), ptr(desc), T_out, t_begin, t_count, fft_size,
+            fft_stride, ptr(window), ptr(plan), ptr(torch.view_as_real(out)), ld))
+    return out
 
 
 # ---------------------------------------------------------------------------
