@@ -7,8 +7,9 @@ One object per .hip/.cpp under csrc/, compiled in parallel, linked into
 csrc/libdanet_hip.so.  The extension library of the conv-bilstm-v1 encoder
 (csrc/conv/*.hip -> csrc/libdanet_conv_hip.so, include/danet_conv_hip.h) is
 built by the same call, and so is the dropout extension (csrc/dropout/*.hip ->
-csrc/libdanet_dropout_hip.so, include/danet_dropout_hip.h) and the dataset front-end extension
-(csrc/prep/*.hip -> csrc/libdanet_prep_hip.so, include/danet_prep_hip.h).  Objects are rebuilt only when their
+csrc/libdanet_dropout_hip.so, include/danet_dropout_hip.h), the dataset front-end extension
+(csrc/prep/*.hip -> csrc/libdanet_prep_hip.so, include/danet_prep_hip.h) and the mixture level
+extension (csrc/mix/*.hip -> csrc/libdanet_mix_hip.so, include/danet_mix_hip.h).  Objects are rebuilt only when their
 source (or a shared header) is newer.  No torch headers are involved: the library is a plain C ABI
 (include/danet_hip.h).
 '''
@@ -31,6 +32,9 @@ DROPOUT_LIB = os.path.join(CSRC, 'libdanet_dropout_hip.so')
 PREP_CSRC = os.path.join(CSRC, 'prep')
 PREP_BUILD = os.path.join(PREP_CSRC, 'build')
 PREP_LIB = os.path.join(CSRC, 'libdanet_prep_hip.so')
+MIX_CSRC = os.path.join(CSRC, 'mix')
+MIX_BUILD = os.path.join(MIX_CSRC, 'build')
+MIX_LIB = os.path.join(CSRC, 'libdanet_mix_hip.so')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # -fvisibility=hidden: only what include/danet_hip.h declares (inside its visibility pragma) is exported
@@ -92,6 +96,7 @@ def build(force=False, verbose=True):
     build_conv(force=force, verbose=verbose)
     build_dropout(force=force, verbose=verbose)
     build_prep(force=force, verbose=verbose)
+    build_mix(force=force, verbose=verbose)
     return LIB
 
 
@@ -143,6 +148,22 @@ def build_prep(force=False, verbose=True):
         print('libdanet_prep_hip.so: %s (%d objects, %s)' % (
             PREP_LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
     return PREP_LIB
+
+
+def build_mix(force=False, verbose=True):
+    '''csrc/mix/*.hip -> csrc/libdanet_mix_hip.so (objects under csrc/mix/build/)'''
+    os.makedirs(MIX_BUILD, exist_ok=True)
+    hdr_m = os.path.getmtime(os.path.join(INCLUDE, 'danet_mix_hip.h'))
+    srcs = sorted(f for f in os.listdir(MIX_CSRC) if f.endswith('.hip'))
+    res = [_compile(s, force, hdr_m, MIX_BUILD, src_dir=MIX_CSRC) for s in srcs]
+    objs = [o for o, _ in res]
+    rebuilt = any(r for _, r in res)
+    if rebuilt or not os.path.exists(MIX_LIB):
+        _link(objs, MIX_LIB, exports=os.path.join(MIX_CSRC, 'exports.map'))
+    if verbose:
+        print('libdanet_mix_hip.so: %s (%d objects, %s)' % (
+            MIX_LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
+    return MIX_LIB
 
 
 def build_variant(name, defs):

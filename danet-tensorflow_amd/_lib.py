@@ -311,6 +311,52 @@ def prep_check(rc):
         raise DanetHipError('libdanet_prep_hip error %d: %s' % (rc, msg.decode() if msg else '?'))
 
 
+# ---- the mixture level extension library (include/danet_mix_hip.h) ----
+# Loaded at the first wavdir batch with MIX_SNR_RANGE or MIX_LEVEL_RANGE set only (ops.mix_power /
+# ops.mix_scale_): a run with both keys null never maps it.
+MIX_LIB_PATH = os.path.join(_HERE, 'csrc', 'libdanet_mix_hip.so')
+MIX_ABI_VERSION = 1
+# name -> (restype, argtypes); mirrors include/danet_mix_hip.h
+MIX_PROTOTYPES = {
+    'danet_mix_abi_version': (c_int, []),
+    'danet_mix_last_error': (ctypes.c_char_p, []),
+    'danet_mix_workspace_bytes': (c_sz, [c_int, c_i64]),
+    'danet_mix_power': (c_int, [c_p, c_int, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_sz]),
+    'danet_mix_scale_c64': (c_int, [c_p, c_int, c_int, c_int, c_p, c_i64, c_p]),
+}
+_mix = None
+
+
+def load_mix():
+    '''dlopen libdanet_mix_hip.so (after torch)'''
+    global _mix
+    if _mix is not None:
+        return _mix
+    with _lock:
+        if _mix is not None:
+            return _mix
+        if not os.path.exists(MIX_LIB_PATH):
+            raise DanetHipError(
+                'libdanet_mix_hip.so not found at %s -- MIX_SNR_RANGE / MIX_LEVEL_RANGE need the HIP '
+                'extension library (there is no CPU fallback); build it with '
+                '`python -c "import __graft_entry__ as g; g.build()"`' % MIX_LIB_PATH)
+        lib = ctypes.CDLL(MIX_LIB_PATH, mode=ctypes.RTLD_LOCAL)
+        for name, (res, args) in MIX_PROTOTYPES.items():
+            fn = getattr(lib, name)      # AttributeError if the symbol is missing
+            fn.restype = res
+            fn.argtypes = args
+        if lib.danet_mix_abi_version() != MIX_ABI_VERSION:
+            raise DanetHipError('libdanet_mix_hip.so ABI version mismatch')
+        _mix = lib
+    return _mix
+
+
+def mix_check(rc):
+    if rc != 0:
+        msg = load_mix().danet_mix_last_error()
+        raise DanetHipError('libdanet_mix_hip error %d: %s' % (rc, msg.decode() if msg else '?'))
+
+
 # ---- switches ------------------------------------------------------------------
 # USER switches (README): DANET_GEMM_X6, DANET_LSTM_FWD_FUSED, DANET_SIDE_STREAMS, DANET_FEED_MODE,
 # DANET_OVERLAP_ALLREDUCE, DANET_ALLREDUCE_TAIL_RATIO, DANET_MAX_STEPS_IN_FLIGHT, DANET_STATUS_HOST, DANET_FUSE_HEADS,

@@ -4,7 +4,8 @@ Datasets.  Only the reference's data-free `toy` generator
 corpora and are out of scope.  `synth` is the speech-shaped 8 kHz
 2-speaker generator the benchmarks use.  `wavdir` trains on a folder of the user's
 own WAV files: waveforms resident in device memory, every batch one launch of the ragged-batch
-STFT kernel (include/danet_prep_hip.h).
+STFT kernel (include/danet_prep_hip.h), and -- with MIX_SNR_RANGE / MIX_LEVEL_RANGE set -- one launch that
+applies the drawn per-utterance gains (include/danet_mix_hip.h).
 '''
 import os
 import random
@@ -136,7 +137,8 @@ def _stft_frames(n_samples, fft_size, fft_stride):
 
 
 class _DescSlot(object):
-    '''one pinned descriptor table + its device copy + the event behind the last upload out of it'''
+    '''one pinned descriptor table (with mixing gains: followed by one float32 per utterance) + its device
+    copy + the event behind the last upload out of it'''
     __slots__ = ('pin', 'dev', 'event', 'used')
 
 
@@ -156,7 +158,17 @@ class WavDirData(Dataset):
     padded batch is not built on the host: ops.stft_batch writes it in one launch.
 
     epoch()         the host-literal form every dataset has: numpy complex64 [batch, T_max, F]
-    epoch_device()  the fast form: device tensors [B, C, T', F], crop included, no host copy'''
+    epoch_device()  the fast form: device tensors [B, C, T', F], crop included, no host copy
+
+    MIXTURE LEVELS (hparams.MIX_SNR_RANGE = R, hparams.MIX_LEVEL_RANGE = L, dB, both default None = off: no
+    launch, no allocation, no draw, libdanet_mix_hip.so not mapped).  The STFT is linear, so a gain on a
+    waveform is a gain on its spectrum: every utterance's mean power is measured once per pool on the device
+    (ops.mix_power), every batch draws its gains on the host by the rule include/danet_mix_hip.h writes out
+    (plan_gains: sources of a group equalised to their geometric-mean power and offset against each other by
+    at most R; the group shifted by one draw from U(-L, L)) and ONE more launch applies them to the batch the
+    STFT kernel wrote (ops.mix_scale_); the gains ride in the pinned ring behind the descriptor table.  Draws
+    come from a RandomState of the dataset's own per subset, seeded by (dist.shard_seed(1337), subset index):
+    `train` runs on across epochs, `valid` / `test` are re-seeded at the start of every sweep.'''
     SUBSETS = ('train', 'valid', 'test')
     DESC_DEPTH = 8        # pinned descriptor tables in flight
     OUT_DEPTH = 3         # output buffers: a yielded batch stays valid while the next two are drawn
@@ -166,6 +178,10 @@ class WavDirData(Dataset):
         self.files, self.lengths, self.offsets, self.frames = {}, {}, {}, {}
         self.pool_host, self.skipped = {}, {}
         self._pool_dev, self._window, self._ring = {}, {}, {}
+        self.mix_snr_range = self.mix_level_range = None      # read from hparams by load_host
+        self.power = {}             # subset -> float64 mean power sum(x^2) / len of every utterance
+        self._mix_rng = {}
+        self._alias = False
 
     # ---- host half -------------------------------------------------------------------------------
     @staticmethod
@@ -189,8 +205,27 @@ class WavDirData(Dataset):
             found += [os.path.join(base, n) for n in names if n.lower().endswith('.wav')]
         return sorted(found)
 
+    @staticmethod
+    def mix_ranges():
+        '''(MIX_SNR_RANGE, MIX_LEVEL_RANGE) as floats or None; anything but null or a finite number >= 0 is a
+        ValueError that names the key'''
+        out = []
+        for key in ('MIX_SNR_RANGE', 'MIX_LEVEL_RANGE'):
+            v = getattr(hparams, key, None)
+            if v is not None:
+                if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float('inf'):
+                    raise ValueError('hparams.%s must be null or a number of dB >= 0, got %r' % (key, v))
+                v = float(v)
+            out.append(v)
+        return tuple(out)
+
+    @property
+    def mix_on(self):
+        return self.mix_snr_range is not None or self.mix_level_range is not None
+
     def load_host(self, out=None):
         '''discover, decode and resample every subset into host pools (no device involved)'''
+        self.mix_snr_range, self.mix_level_range = self.mix_ranges()
         root = hparams.DATASET_DIR
         if root is None:
             raise ValueError('the wavdir dataset needs hparams.DATASET_DIR: the folder that holds '
@@ -251,6 +286,60 @@ class WavDirData(Dataset):
             cnt = crop_len
         return T_max, pads, beg, cnt
 
+    # ---- mixture levels: the gain rule (host, no device; include/danet_mix_hip.h) ----------------------
+    @staticmethod
+    def plan_gains(powers, rng, n_src, snr_range=None, level_range=None):
+        '''float32 gains of one batch: `powers` the mean powers of its rows (groups of n_src consecutive rows),
+        `rng` the RandomState the draws come from -- per group the n_src - 1 offsets (snr_range set), then the
+        level (level_range set)'''
+        P = np.asarray(powers, dtype=np.float64).reshape(-1, n_src)
+        B, k = len(P), (n_src - 1 if snr_range is not None else 0)
+        lo = np.asarray([-snr_range if c < k else -level_range for c in range(k + (level_range is not None))],
+                        dtype=np.float64)
+        # ONE call draws the whole batch: numpy fills an array draw by draw in row-major order, each as the scalar
+        # rng.uniform(lo, hi) would (lo + (hi - lo) * next double), i.e. group by group: offsets, then level
+        x = rng.uniform(np.tile(lo, (B, 1)), np.tile(-lo, (B, 1))) if len(lo) else np.zeros((B, 0))
+        u = np.concatenate([np.zeros((B, 1)), x[:, :k]], axis=1)
+        d = u - u.sum(axis=1, keepdims=True) / n_src
+        level = x[:, k:] if level_range is not None else 0.0
+        live = P > 0
+        gains = 10.0 ** ((d + level) / 20.0)
+        if snr_range is not None:
+            safe = np.where(live, P, 1.0)
+            G = np.exp(np.log(safe).sum(axis=1, keepdims=True) / np.maximum(live.sum(axis=1, keepdims=True), 1))
+            gains = np.sqrt(G / safe) * gains
+        return np.where(live, gains, 1.0).reshape(-1).astype(np.float32)
+
+    def _pool_key(self, subset):
+        return 'test' if (subset == 'valid' and self._alias) else subset
+
+    def mix_stream(self, subset):
+        '''the RandomState `subset`'s gains are drawn from (None with both keys null): the train stream is
+        created once, the valid / test streams anew by every call -- the start of a sweep'''
+        if not self.mix_on:
+            return None
+        if subset != 'train' or subset not in self._mix_rng:
+            from . import dist
+            self._mix_rng[subset] = np.random.RandomState([dist.shard_seed(1337), self.SUBSETS.index(subset)])
+        return self._mix_rng[subset]
+
+    def plan_epoch(self, subset, batch_size, shuffle=False, crop_len=None, crop=False):
+        '''the host plan of one epoch, per batch (idx, T_max, pads, t_begin, t_count, gains): plan_indices, then
+        per batch plan_batch and -- with a MIX_* key set -- plan_gains on self.power (else gains is None and
+        nothing is drawn).  `random` / `np.random` advance exactly as without the keys.'''
+        rng = self.mix_stream(subset)
+        C = hparams.MAX_N_SIGNAL
+        if rng is not None and batch_size % C:
+            raise ValueError('wavdir: with MIX_SNR_RANGE / MIX_LEVEL_RANGE set the batch size must be a multiple '
+                             'of MAX_N_SIGNAL = %d (got %d): gains are drawn per group of sources' % (C, batch_size))
+        for idx in self.plan_indices(subset, batch_size, shuffle):
+            T_max, pads, beg, cnt = self.plan_batch(subset, idx, crop_len, crop)
+            gains = None
+            if rng is not None:
+                gains = self.plan_gains(self.power[self._pool_key(subset)][idx], rng, C,
+                                        self.mix_snr_range, self.mix_level_range)
+            yield idx, T_max, pads, beg, cnt, gains
+
     # ---- device half -----------------------------------------------------------------------------
     @staticmethod
     def _device(device=None):
@@ -263,11 +352,22 @@ class WavDirData(Dataset):
     def upload_pool(self, subset, device):
         '''the subset's float32 pool on `device` (uploaded once)'''
         import torch
-        key = ('test' if (subset == 'valid' and self._alias) else subset, str(device))
+        key = (self._pool_key(subset), str(device))
         pool = self._pool_dev.get(key)
         if pool is None:
             pool = self._pool_dev[key] = torch.from_numpy(self.pool_host[subset]).to(device)
         return pool
+
+    def power_table(self, subset, pool):
+        '''float64 mean power of every utterance of the subset, measured on the device once (ops.mix_power on
+        the uploaded pool; an aliased `valid` shares `test`'s table)'''
+        key = self._pool_key(subset)
+        table = self.power.get(key)
+        if table is None:
+            from . import ops
+            sums = ops.mix_power(pool, self.offsets[subset], self.lengths[subset]).cpu().numpy()
+            table = self.power[key] = sums / self.lengths[subset].astype(np.float64)
+        return table
 
     def _window_on(self, device):
         import torch
@@ -282,37 +382,44 @@ class WavDirData(Dataset):
         the current CUDA device; cli passes the model's, so the pool is uploaded once, where the model is)'''
         if not self.is_loaded:
             raise RuntimeError('Dataset is not loaded.')
+        import torch
         from . import ops
         device = self._device(device)
         pool, window = self.upload_pool(subset, device), self._window_on(device)
-        for idx in self.plan_indices(subset, batch_size, shuffle):
-            T_max, pads, _beg, _cnt = self.plan_batch(subset, idx)
+        if self.mix_on:
+            self.power_table(subset, pool)
+        for idx, T_max, pads, _beg, _cnt, gains in self.plan_epoch(subset, batch_size, shuffle):
             desc = ops.prep_desc(self.offsets[subset][idx], self.lengths[subset][idx], pads, T_max,
                                  pool.numel(), hparams.FFT_SIZE, hparams.FFT_STRIDE)
             spectra = ops.stft_batch(pool, desc, T_max, window, hparams.FFT_SIZE, hparams.FFT_STRIDE,
                                      t_begin=0, t_count=T_max)
+            if gains is not None:
+                ops.mix_scale_(spectra, torch.from_numpy(gains).to(device))
             yield (spectra.cpu().numpy(),)
 
     def _take_ring(self, device, n_utt):
         import torch
+        from . import ops
+        row = ops.PREP_DESC_DTYPE.itemsize + (4 if self.mix_on else 0)      # + one float32 gain
         ring = self._ring.get(str(device))
-        if ring is None or ring['n_utt'] < n_utt:
-            from . import ops
+        if ring is None or ring['n_utt'] < n_utt or ring['row'] < row:
             slots = []
             for _ in range(self.DESC_DEPTH):
                 s = _DescSlot()
-                s.pin = torch.zeros(n_utt * ops.PREP_DESC_DTYPE.itemsize, dtype=torch.uint8).pin_memory()
-                s.dev = torch.zeros(n_utt * ops.PREP_DESC_DTYPE.itemsize, dtype=torch.uint8, device=device)
+                s.pin = torch.zeros(n_utt * row, dtype=torch.uint8).pin_memory()
+                s.dev = torch.zeros(n_utt * row, dtype=torch.uint8, device=device)
                 s.event, s.used = torch.cuda.Event(), False
                 slots.append(s)
-            ring = self._ring[str(device)] = dict(n_utt=n_utt, slots=slots, out=[None] * self.OUT_DEPTH, k=0)
+            ring = self._ring[str(device)] = dict(n_utt=n_utt, row=row, slots=slots, out=[None] * self.OUT_DEPTH,
+                                                  k=0)
         return ring
 
     def epoch_device(self, subset, batch_size, shuffle=False, device=None, crop_len=None):
         '''the batches of epoch() -- same index plan, same pad draws -- followed by the crop draw of
         feed.to_batch_host, as complex64 DEVICE tensors [BATCH_SIZE, MAX_N_SIGNAL, T', F]: one
         ops.stft_batch launch per batch computes only the cropped frames; per batch a 24-byte row per
-        utterance crosses PCIe, from a pinned ring, without a host wait.  Everything is enqueued on the
+        utterance (28 with mixing gains, followed by their one launch) crosses PCIe, from a pinned ring,
+        without a host wait.  Everything is enqueued on the
         stream that is current in the consumer.  LIFETIME: a yielded tensor is a view of one of
         OUT_DEPTH reused device buffers and stays valid until the consumer has asked for OUT_DEPTH - 1
         more batches (the same rule as feed.BatchFeed; clone it to keep it longer).'''
@@ -322,15 +429,20 @@ class WavDirData(Dataset):
         F, B, C = hparams.FEATURE_SIZE, hparams.BATCH_SIZE, hparams.MAX_N_SIGNAL
         assert batch_size == B * C, (batch_size, B, C)
         pool, window = self.upload_pool(subset, device), self._window_on(device)
+        if self.mix_on:
+            self.power_table(subset, pool)
         ring = self._take_ring(device, batch_size)
-        for idx in self.plan_indices(subset, batch_size, shuffle):
-            T_max, pads, beg, cnt = self.plan_batch(subset, idx, crop_len, crop=True)
-            out = self._emit(device, pool, window, ring, subset, idx, T_max, pads, beg, cnt)
+        for idx, T_max, pads, beg, cnt, gains in self.plan_epoch(subset, batch_size, shuffle, crop_len, crop=True):
+            if gains is None:
+                out = self._emit(device, pool, window, ring, subset, idx, T_max, pads, beg, cnt)
+            else:
+                out = self._emit(device, pool, window, ring, subset, idx, T_max, pads, beg, cnt, gains=gains)
             yield out.view(B, C, cnt, F)
 
-    def _emit(self, device, pool, window, ring, subset, idx, T_max, pads, beg, cnt):
-        '''the device half of one batch: descriptor table through the pinned ring, one launch into the
-        next output buffer -> complex64 [batch, cnt, F]'''
+    def _emit(self, device, pool, window, ring, subset, idx, T_max, pads, beg, cnt, gains=None):
+        '''the device half of one batch: descriptor table (and the gains behind it, in the same copy) through
+        the pinned ring, one launch into the next output buffer (and one that scales it in place)
+        -> complex64 [batch, cnt, F]'''
         import torch
         from . import ops
         N, S, F = hparams.FFT_SIZE, hparams.FFT_STRIDE, hparams.FEATURE_SIZE
@@ -343,8 +455,11 @@ class WavDirData(Dataset):
         table = slot.pin[:batch_size * row].numpy().view(ops.PREP_DESC_DTYPE)
         ops.prep_desc(self.offsets[subset][idx], self.lengths[subset][idx], pads, T_max,
                       pool.numel(), N, S, out=table)
-        dev_table = slot.dev[:batch_size * row]
-        dev_table.copy_(slot.pin[:batch_size * row], non_blocking=True)
+        dev_table, sent = slot.dev[:batch_size * row], batch_size * row
+        if gains is not None:             # float32 [batch] right behind the table: one copy carries both
+            sent += batch_size * 4
+            slot.pin[batch_size * row:sent].numpy().view(np.float32)[:] = gains
+        slot.dev[:sent].copy_(slot.pin[:sent], non_blocking=True)
         slot.event.record(torch.cuda.current_stream(device))
         slot.used = True
         n = batch_size * cnt * F
@@ -353,4 +468,6 @@ class WavDirData(Dataset):
             buf = ring['out'][k % self.OUT_DEPTH] = torch.empty(n, dtype=torch.complex64, device=device)
         out = buf[:n].view(batch_size, cnt, F)
         ops.stft_batch(pool, dev_table, T_max, window, N, S, t_begin=beg, t_count=cnt, out=out)
+        if gains is not None:
+            ops.mix_scale_(out, slot.dev[batch_size * row:sent].view(torch.float32))
         return out

@@ -18,6 +18,9 @@ unchanged.  Differences, all deliberate:
   `tf.nn.dropout` where `_lyr_bilstm` has it (`app/modules.py:137`).  The
   default 1.0 is exactly the reference's behaviour.
 * `DATASET_DIR` (default None) names the folder the `wavdir` dataset reads.
+* `MIX_SNR_RANGE` / `MIX_LEVEL_RANGE` (dB, default None = off) make the `wavdir` dataset mix
+  its sources at a drawn relative level / shift the whole mixture by a drawn level
+  (the reference's `# TODO add mixing coeff ?`, `main.py:230`); every other dataset ignores them.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -68,6 +71,9 @@ DEFAULTS = {
     'KMEANS_ITERS': 10,
     # root folder of the `wavdir` dataset: DATASET_DIR/{train,valid,test}/**/*.wav (not in the reference)
     'DATASET_DIR': None,
+    # mixture level control of the `wavdir` dataset, dB, None = off (not in the reference; include/danet_mix_hip.h)
+    'MIX_SNR_RANGE': None,
+    'MIX_LEVEL_RANGE': None,
 }
 
 

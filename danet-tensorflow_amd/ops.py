@@ -471,6 +471,62 @@ def stft_batch(pool, desc, T_out, window, fft_size, fft_stride, t_begin=0, t_cou
     return out
 
 
+# ---- mixture level control of the wavdir dataset (include/danet_mix_hip.h) --------------------------
+# On the extension library libdanet_mix_hip.so, mapped at the first call: a wavdir run with
+# MIX_SNR_RANGE and MIX_LEVEL_RANGE null never gets here.
+def mix_power(pool, offsets, lengths, max_len=None):
+    '''sum of squares of every row [offset, offset + length) of the float32 device vector `pool`
+    -> float64 DEVICE vector [n] (danet_mix_power: float64 accumulation, a fixed reduction tree).
+    offsets, lengths: host integer sequences (validated here: a row outside the pool is a ValueError
+    before any upload or launch) or int64 device tensors the caller has validated (the kernel clamps,
+    and `max_len`, an upper bound of the lengths, must then be given).'''
+    assert pool.is_cuda and pool.dtype == torch.float32 and pool.dim() == 1 and pool.is_contiguous()
+    if not torch.is_tensor(offsets):
+        offsets, lengths = np.asarray(offsets, dtype=np.int64), np.asarray(lengths, dtype=np.int64)
+        if offsets.shape != lengths.shape or offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError('mix_power: offsets and lengths must be two vectors of one length >= 1')
+        bad = np.nonzero((offsets < 0) | (lengths < 0) | (offsets + lengths > pool.numel()))[0]
+        if len(bad):
+            u = int(bad[0])
+            raise ValueError('mix_power: utterance %d [%d, %d) is outside the pool of %d samples'
+                             % (u, offsets[u], offsets[u] + lengths[u], pool.numel()))
+        if max_len is None:
+            max_len = int(lengths.max())
+        offsets, lengths = torch.from_numpy(offsets).to(pool.device), torch.from_numpy(lengths).to(pool.device)
+    if max_len is None:
+        raise ValueError('mix_power: device tables need max_len')
+    for t in (offsets, lengths):
+        assert t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous()
+    n = offsets.numel()
+    assert lengths.numel() == n
+    L = _lib.load_mix()
+    nbytes = L.danet_mix_workspace_bytes(n, int(max_len))
+    if nbytes == ctypes.c_size_t(-1).value:
+        _lib.mix_check(-1)
+    ws = _lib.workspace(nbytes, pool.device, 'mix') if nbytes else None
+    out = torch.empty(n, dtype=torch.float64, device=pool.device)
+    with _lib.timed('mix_power'):
+        _lib.mix_check(L.danet_mix_power(_lib.stream(), n, ptr(pool), pool.numel(), ptr(offsets), ptr(lengths),
+                                         int(max_len), ptr(out), ptr(ws), nbytes))
+    return out
+
+
+def mix_scale_(batch, gains):
+    '''batch[u] *= gains[u] in place, ONE launch (danet_mix_scale_c64): complex64 device tensor
+    [n_utt, t_count, F] whose last dimension is contiguous (its row pitch is used; the gaps are never
+    touched), float32 device vector [n_utt].  Every part becomes the single rounding fl(g * x).'''
+    assert batch.is_cuda and batch.dtype == torch.complex64 and batch.dim() == 3, (batch.dtype, batch.shape)
+    n_utt, t_count, F = batch.shape
+    assert gains.is_cuda and gains.dtype == torch.float32 and gains.dim() == 1 and gains.is_contiguous()
+    assert gains.numel() == n_utt and gains.device == batch.device
+    ld = batch.stride(1) if t_count > 1 else max(batch.stride(1), F)
+    assert batch.stride(2) == 1 and (n_utt == 1 or batch.stride(0) == t_count * ld), batch.stride()
+    with _lib.timed('mix_scale'):
+        _lib.mix_check(_lib.load_mix().danet_mix_scale_c64(
+            _lib.stream(), n_utt, t_count, F, ptr(torch.view_as_real(batch)), ld, ptr(gains)))
+    return batch
+
+
 # ---------------------------------------------------------------------------
 # LSTM layer (both directions), raw forward / backward on time-major tensors
 # ---------------------------------------------------------------------------
