@@ -1,18 +1,21 @@
 '''
-Builds libdanet_hip.so (gfx950 only) in-tree with hipcc.
+Builds the five HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
-One object per .hip/.cpp under csrc/, compiled in parallel, linked into
-csrc/libdanet_hip.so.  The extension library of the conv-bilstm-v1 encoder
-(csrc/conv/*.hip -> csrc/libdanet_conv_hip.so, include/danet_conv_hip.h) is
-built by the same call, and so is the dropout extension (csrc/dropout/*.hip ->
-csrc/libdanet_dropout_hip.so, include/danet_dropout_hip.h), the dataset front-end extension
-(csrc/prep/*.hip -> csrc/libdanet_prep_hip.so, include/danet_prep_hip.h) and the mixture level
-extension (csrc/mix/*.hip -> csrc/libdanet_mix_hip.so, include/danet_mix_hip.h).  Objects are rebuilt only when their
-source (or a shared header) is newer.  No torch headers are involved: the library is a plain C ABI
-(include/danet_hip.h).
+    library (under csrc/)         sources                  rebuilt when one of these headers is newer
+    libdanet_hip.so               csrc/*.hip, csrc/*.cpp   csrc/*.h, include/*.h
+    libdanet_conv_hip.so          csrc/conv/*.hip          include/danet_conv_hip.h, csrc/conv/*.h
+    libdanet_dropout_hip.so       csrc/dropout/*.hip       include/danet_dropout_hip.h
+    libdanet_prep_hip.so          csrc/prep/*.hip          include/danet_prep_hip.h
+    libdanet_mix_hip.so           csrc/mix/*.hip           include/danet_mix_hip.h
+
+One object per source under <source directory>/build/, compiled in parallel and linked with the
+exports.map of the source directory; an object is rebuilt only when its source or one of its library's
+headers is newer.  No torch headers are involved: every library is a plain C ABI (include/*.h).
 '''
+import collections
+import glob
 import os
 import subprocess
 import sys
@@ -21,43 +24,39 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
-BUILD = os.path.join(CSRC, 'build')
-LIB = os.path.join(CSRC, 'libdanet_hip.so')
-CONV_CSRC = os.path.join(CSRC, 'conv')
-CONV_BUILD = os.path.join(CONV_CSRC, 'build')
-CONV_LIB = os.path.join(CSRC, 'libdanet_conv_hip.so')
-DROPOUT_CSRC = os.path.join(CSRC, 'dropout')
-DROPOUT_BUILD = os.path.join(DROPOUT_CSRC, 'build')
-DROPOUT_LIB = os.path.join(CSRC, 'libdanet_dropout_hip.so')
-PREP_CSRC = os.path.join(CSRC, 'prep')
-PREP_BUILD = os.path.join(PREP_CSRC, 'build')
-PREP_LIB = os.path.join(CSRC, 'libdanet_prep_hip.so')
-MIX_CSRC = os.path.join(CSRC, 'mix')
-MIX_BUILD = os.path.join(MIX_CSRC, 'build')
-MIX_LIB = os.path.join(CSRC, 'libdanet_mix_hip.so')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-# -fvisibility=hidden: only what include/danet_hip.h declares (inside its visibility pragma) is exported
+# -fvisibility=hidden: only what the library's header declares (inside its visibility pragma) is exported
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden', '-I' + INCLUDE,
          '-I' + CSRC, '-Wno-unused-result']
 # extra -D switches for A/B builds, e.g. DANET_BUILD_DEFS='-DBK=32' (use --force)
 FLAGS += os.environ.get('DANET_BUILD_DEFS', '').split()
 
-
-def _sources():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(('.hip', '.cpp')))
-
-
-def _headers_mtime():
-    m = 0.0
-    for d in (CSRC, INCLUDE):
-        for f in os.listdir(d):
-            if f.endswith('.h'):
-                m = max(m, os.path.getmtime(os.path.join(d, f)))
-    return m
+# out: the shared object; src_dir: its sources, its exports.map and (under build/) its objects;
+# headers: glob patterns of the headers whose change rebuilds every object of the library
+Library = collections.namedtuple('Library', 'out src_dir headers')
 
 
-def _compile(src, force, hdr_m, bdir=BUILD, defs=(), src_dir=CSRC):
+def _extension(name, *more_headers):
+    src_dir = os.path.join(CSRC, name)
+    return Library(os.path.join(CSRC, 'libdanet_%s_hip.so' % name), src_dir,
+                   (os.path.join(INCLUDE, 'danet_%s_hip.h' % name),) + more_headers)
+
+
+CORE = Library(os.path.join(CSRC, 'libdanet_hip.so'), CSRC, (os.path.join(CSRC, '*.h'), os.path.join(INCLUDE, '*.h')))
+CONV = _extension('conv', os.path.join(CSRC, 'conv', '*.h'))
+DROPOUT = _extension('dropout')
+PREP = _extension('prep')
+MIX = _extension('mix')
+LIBRARIES = (CORE, CONV, DROPOUT, PREP, MIX)      # build() builds them in this order
+LIB, CONV_LIB, DROPOUT_LIB, PREP_LIB, MIX_LIB = (spec.out for spec in LIBRARIES)
+
+
+def _sources(src_dir):
+    return sorted(f for f in os.listdir(src_dir) if f.endswith(('.hip', '.cpp')))
+
+
+def _compile(src_dir, src, bdir, force, hdr_m, defs=()):
     obj = os.path.join(bdir, os.path.splitext(src)[0] + '.o')
     sp = os.path.join(src_dir, src)
     if (not force and os.path.exists(obj)
@@ -72,98 +71,55 @@ def _compile(src, force, hdr_m, bdir=BUILD, defs=(), src_dir=CSRC):
     return obj, True
 
 
-def _link(objs, out, exports=os.path.join(CSRC, 'exports.map')):
+def _compile_all(src_dir, bdir, force, hdr_m, defs=()):
+    '''-> [(object, rebuilt)] of every source of src_dir, in sorted order'''
+    os.makedirs(bdir, exist_ok=True)
+    srcs = _sources(src_dir)
+    with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
+        return list(ex.map(lambda s: _compile(src_dir, s, bdir, force, hdr_m, defs), srcs))
+
+
+def _link(objs, out, src_dir):
     cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC',
-           '-Wl,--version-script=' + exports, '-o', out] + objs
+           '-Wl,--version-script=' + os.path.join(src_dir, 'exports.map'), '-o', out] + objs
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError('link failed:\n%s\n%s' % (r.stdout, r.stderr))
 
 
-def build(force=False, verbose=True):
-    os.makedirs(BUILD, exist_ok=True)
-    hdr_m = _headers_mtime()
-    srcs = _sources()
-    with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
-        res = list(ex.map(lambda s: _compile(s, force, hdr_m), srcs))
+def _build_library(spec, force, verbose):
+    hdr_m = max((os.path.getmtime(h) for pattern in spec.headers for h in glob.glob(pattern)), default=0.0)
+    res = _compile_all(spec.src_dir, os.path.join(spec.src_dir, 'build'), force, hdr_m)
     objs = [o for o, _ in res]
     rebuilt = any(r for _, r in res)
-    if rebuilt or not os.path.exists(LIB):
-        _link(objs, LIB)
+    if rebuilt or not os.path.exists(spec.out):
+        _link(objs, spec.out, spec.src_dir)
     if verbose:
-        print('libdanet_hip.so: %s (%d objects, %s)' % (
-            LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
-    build_conv(force=force, verbose=verbose)
-    build_dropout(force=force, verbose=verbose)
-    build_prep(force=force, verbose=verbose)
-    build_mix(force=force, verbose=verbose)
+        print('%s: %s (%d objects, %s)' % (
+            os.path.basename(spec.out), spec.out, len(objs), 'rebuilt' if rebuilt else 'up to date'))
+    return spec.out
+
+
+def build(force=False, verbose=True):
+    for spec in LIBRARIES:
+        _build_library(spec, force, verbose)
     return LIB
 
 
 def build_conv(force=False, verbose=True):
-    '''csrc/conv/*.hip -> csrc/libdanet_conv_hip.so (objects under csrc/conv/build/)'''
-    os.makedirs(CONV_BUILD, exist_ok=True)
-    hdr_m = max([os.path.getmtime(os.path.join(INCLUDE, 'danet_conv_hip.h'))] +
-                [os.path.getmtime(os.path.join(CONV_CSRC, f)) for f in os.listdir(CONV_CSRC) if f.endswith('.h')])
-    srcs = sorted(f for f in os.listdir(CONV_CSRC) if f.endswith('.hip'))
-    with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
-        res = list(ex.map(lambda s: _compile(s, force, hdr_m, CONV_BUILD, src_dir=CONV_CSRC), srcs))
-    objs = [o for o, _ in res]
-    rebuilt = any(r for _, r in res)
-    if rebuilt or not os.path.exists(CONV_LIB):
-        _link(objs, CONV_LIB, exports=os.path.join(CONV_CSRC, 'exports.map'))
-    if verbose:
-        print('libdanet_conv_hip.so: %s (%d objects, %s)' % (
-            CONV_LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
-    return CONV_LIB
+    return _build_library(CONV, force, verbose)
 
 
 def build_dropout(force=False, verbose=True):
-    '''csrc/dropout/*.hip -> csrc/libdanet_dropout_hip.so (objects under csrc/dropout/build/)'''
-    os.makedirs(DROPOUT_BUILD, exist_ok=True)
-    hdr_m = os.path.getmtime(os.path.join(INCLUDE, 'danet_dropout_hip.h'))
-    srcs = sorted(f for f in os.listdir(DROPOUT_CSRC) if f.endswith('.hip'))
-    res = [_compile(s, force, hdr_m, DROPOUT_BUILD, src_dir=DROPOUT_CSRC) for s in srcs]
-    objs = [o for o, _ in res]
-    rebuilt = any(r for _, r in res)
-    if rebuilt or not os.path.exists(DROPOUT_LIB):
-        _link(objs, DROPOUT_LIB, exports=os.path.join(DROPOUT_CSRC, 'exports.map'))
-    if verbose:
-        print('libdanet_dropout_hip.so: %s (%d objects, %s)' % (
-            DROPOUT_LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
-    return DROPOUT_LIB
+    return _build_library(DROPOUT, force, verbose)
 
 
 def build_prep(force=False, verbose=True):
-    '''csrc/prep/*.hip -> csrc/libdanet_prep_hip.so (objects under csrc/prep/build/)'''
-    os.makedirs(PREP_BUILD, exist_ok=True)
-    hdr_m = os.path.getmtime(os.path.join(INCLUDE, 'danet_prep_hip.h'))
-    srcs = sorted(f for f in os.listdir(PREP_CSRC) if f.endswith('.hip'))
-    res = [_compile(s, force, hdr_m, PREP_BUILD, src_dir=PREP_CSRC) for s in srcs]
-    objs = [o for o, _ in res]
-    rebuilt = any(r for _, r in res)
-    if rebuilt or not os.path.exists(PREP_LIB):
-        _link(objs, PREP_LIB, exports=os.path.join(PREP_CSRC, 'exports.map'))
-    if verbose:
-        print('libdanet_prep_hip.so: %s (%d objects, %s)' % (
-            PREP_LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
-    return PREP_LIB
+    return _build_library(PREP, force, verbose)
 
 
 def build_mix(force=False, verbose=True):
-    '''csrc/mix/*.hip -> csrc/libdanet_mix_hip.so (objects under csrc/mix/build/)'''
-    os.makedirs(MIX_BUILD, exist_ok=True)
-    hdr_m = os.path.getmtime(os.path.join(INCLUDE, 'danet_mix_hip.h'))
-    srcs = sorted(f for f in os.listdir(MIX_CSRC) if f.endswith('.hip'))
-    res = [_compile(s, force, hdr_m, MIX_BUILD, src_dir=MIX_CSRC) for s in srcs]
-    objs = [o for o, _ in res]
-    rebuilt = any(r for _, r in res)
-    if rebuilt or not os.path.exists(MIX_LIB):
-        _link(objs, MIX_LIB, exports=os.path.join(MIX_CSRC, 'exports.map'))
-    if verbose:
-        print('libdanet_mix_hip.so: %s (%d objects, %s)' % (
-            MIX_LIB, len(objs), 'rebuilt' if rebuilt else 'up to date'))
-    return MIX_LIB
+    return _build_library(MIX, force, verbose)
 
 
 def build_variant(name, defs):
@@ -173,12 +129,8 @@ def build_variant(name, defs):
     tools/trace_lstm.py); loaded instead of the product library when DANET_LIB_PATH points at it
     (tests / tools only).  Objects under csrc/build_<name>/.'''
     out = os.path.join(CSRC, 'libdanet_hip_%s.so' % name)
-    bdir = os.path.join(CSRC, 'build_' + name)
-    os.makedirs(bdir, exist_ok=True)
-    srcs = _sources()
-    with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
-        res = list(ex.map(lambda s: _compile(s, True, 0.0, bdir, defs), srcs))
-    _link([o for o, _ in res], out)
+    res = _compile_all(CSRC, os.path.join(CSRC, 'build_' + name), True, 0.0, defs)
+    _link([o for o, _ in res], out, CSRC)
     return out
 
 

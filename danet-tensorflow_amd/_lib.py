@@ -1,22 +1,24 @@
 '''
-ctypes binding of libdanet_hip.so (the C ABI declared in include/danet_hip.h).
+ctypes binding of the five HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+libdanet_hip.so and the conv, dropout, prep and mix extension libraries.  Each is described once, by a
+record of LIBRARIES; one loader (_load) and one error check (_check) serve them all.
 
-There is NO fallback: if the shared library is missing or a call fails, a
+There is NO fallback: if a shared library is missing or a call fails, a
 RuntimeError is raised.  PyTorch is used only to own device memory and streams;
 tensors cross the boundary as raw device pointers.
 '''
+import collections
 import ctypes
 import os
 import threading
 
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
-LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libdanet_hip.so')
+_CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 
-c_int, c_i64, c_f32, c_sz, c_p = (ctypes.c_int, ctypes.c_int64, ctypes.c_float,
-                                  ctypes.c_size_t, ctypes.c_void_p)
+c_int, c_i64, c_f32, c_sz, c_p, c_u32 = (ctypes.c_int, ctypes.c_int64, ctypes.c_float,
+                                         ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32)
+
 
 class GemmPack(ctypes.Structure):
     '''danet_gemm_pack_t (include/danet_hip.h)'''
@@ -70,7 +72,6 @@ PROTOTYPES = {
     'danet_lstm_train_prefill': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_p),
                                          ctypes.POINTER(c_p), ctypes.POINTER(c_p)]),
     'danet_lstm_fwd_fused_supported': (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    'danet_lstm_fwd_fused_supported': (c_int, [c_int, c_int, c_int, c_int, c_int]),
     'danet_lstm_fwd_fused': (c_int, [c_p, c_int, c_int, c_int, c_int, c_p, c_int, c_int, c_p, c_p,
                                      c_int, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_sz, c_p,
                                      c_int]),
@@ -96,8 +97,6 @@ PROTOTYPES = {
                                    c_p, c_p, c_p, c_sz]),
     'danet_separate_pit_bwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_i64, c_int, c_p, c_p, c_p,
                                        c_p, c_p, c_p, c_p, c_f32, c_p, c_p, c_p, c_p, c_sz]),
-    'danet_separate_pit_bwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_i64, c_int, c_p, c_p, c_p,
-                                       c_p, c_p, c_p, c_p, c_f32, c_p, c_p, c_p, c_p, c_sz]),
     'danet_separate_pit_fwd_records': (c_int, [c_p, c_int, c_int, c_int, c_int, c_i64, c_int, c_p, c_p,
                                                c_p, c_p, c_p, c_p, c_p, c_p]),
     'danet_separate_pit_final': (c_int, [c_p, c_int, c_int, c_i64, c_f32, c_p, c_p, c_p, c_p]),
@@ -115,48 +114,6 @@ PROTOTYPES = {
     'danet_adam_clip_step': (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_f32, c_f32, c_f32, c_f32,
                                      c_f32, c_f32, c_int]),
 }
-
-_lib = None
-_lock = threading.Lock()
-
-
-class DanetHipError(RuntimeError):
-    pass
-
-
-def load():
-    '''dlopen libdanet_hip.so (after torch, so both share ONE libamdhip64).'''
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is not None:
-            return _lib
-        if not os.path.exists(LIB_PATH):
-            raise DanetHipError(
-                'libdanet_hip.so not found at %s -- the HIP extension is required '
-                '(there is no CPU fallback); build it with '
-                '`python -c "import __graft_entry__ as g; g.build()"`' % LIB_PATH)
-        # torch already mapped its bundled libamdhip64.so (SONAME libamdhip64.so.7);
-        # our DT_NEEDED of the same SONAME resolves to that copy.
-        lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_LOCAL)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(lib, name)      # AttributeError if the symbol is missing
-            fn.restype = res
-            fn.argtypes = args
-        if lib.danet_abi_version() != 7:
-            raise DanetHipError('libdanet_hip.so ABI version mismatch')
-        _lib = lib
-        apply_env_options()
-    return _lib
-
-
-# ---- the extension library of the conv-bilstm-v1 encoder (include/danet_conv_hip.h) ----
-# A separate shared object with its own ABI version: the core's table above stays exactly the core
-# header's.  Missing library = hard error, as for the core.
-CONV_LIB_PATH = os.path.join(_HERE, 'csrc', 'libdanet_conv_hip.so')
-CONV_ABI_VERSION = 1
-
 
 class ConvDesc(ctypes.Structure):
     '''danet_conv_desc_t (include/danet_conv_hip.h)'''
@@ -177,52 +134,7 @@ CONV_PROTOTYPES = {
     'danet_conv_add': (c_int, [c_p, c_i64, c_p, c_p, c_p]),
 }
 CONV_WS_BWD_WEIGHT = 0
-_conv = None
 
-
-def load_conv():
-    '''dlopen libdanet_conv_hip.so (after torch and the core library)'''
-    global _conv
-    if _conv is not None:
-        return _conv
-    with _lock:
-        if _conv is not None:
-            return _conv
-        if not os.path.exists(CONV_LIB_PATH):
-            raise DanetHipError(
-                'libdanet_conv_hip.so not found at %s -- the conv-bilstm-v1 encoder needs the HIP '
-                'extension library (there is no CPU fallback); build it with '
-                '`python -c "import __graft_entry__ as g; g.build()"`' % CONV_LIB_PATH)
-        lib = ctypes.CDLL(CONV_LIB_PATH, mode=ctypes.RTLD_LOCAL)
-        for name, (res, args) in CONV_PROTOTYPES.items():
-            fn = getattr(lib, name)      # AttributeError if the symbol is missing
-            fn.restype = res
-            fn.argtypes = args
-        if lib.danet_conv_abi_version() != CONV_ABI_VERSION:
-            raise DanetHipError('libdanet_conv_hip.so ABI version mismatch')
-        _conv = lib
-    return _conv
-
-
-def conv_check(rc):
-    if rc != 0:
-        msg = load_conv().danet_conv_last_error()
-        raise DanetHipError('libdanet_conv_hip error %d: %s' % (rc, msg.decode() if msg else '?'))
-
-
-def conv_ws_bytes(op, desc):
-    '''danet_conv_workspace_bytes(op, desc)'''
-    n = load_conv().danet_conv_workspace_bytes(op, ctypes.byref(desc))
-    if n == ctypes.c_size_t(-1).value:
-        conv_check(-1)
-    return n
-
-
-# ---- the dropout extension library (include/danet_dropout_hip.h) ----
-# Loaded at the first call with keep < 1 only: a run with DROPOUT_KEEP_PROB = 1 never maps it.
-DROPOUT_LIB_PATH = os.path.join(_HERE, 'csrc', 'libdanet_dropout_hip.so')
-DROPOUT_ABI_VERSION = 1
-c_u32 = ctypes.c_uint32
 # name -> (restype, argtypes); mirrors include/danet_dropout_hip.h
 DROPOUT_PROTOTYPES = {
     'danet_dropout_abi_version': (c_int, []),
@@ -230,44 +142,7 @@ DROPOUT_PROTOTYPES = {
     'danet_dropout_apply': (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_u32, c_f32, c_u32, c_u32,
                                     c_u32, c_u32]),
 }
-_dropout = None
 
-
-def load_dropout():
-    '''dlopen libdanet_dropout_hip.so (after torch and the core library)'''
-    global _dropout
-    if _dropout is not None:
-        return _dropout
-    with _lock:
-        if _dropout is not None:
-            return _dropout
-        if not os.path.exists(DROPOUT_LIB_PATH):
-            raise DanetHipError(
-                'libdanet_dropout_hip.so not found at %s -- DROPOUT_KEEP_PROB < 1 needs the HIP '
-                'extension library (there is no CPU fallback); build it with '
-                '`python -c "import __graft_entry__ as g; g.build()"`' % DROPOUT_LIB_PATH)
-        lib = ctypes.CDLL(DROPOUT_LIB_PATH, mode=ctypes.RTLD_LOCAL)
-        for name, (res, args) in DROPOUT_PROTOTYPES.items():
-            fn = getattr(lib, name)      # AttributeError if the symbol is missing
-            fn.restype = res
-            fn.argtypes = args
-        if lib.danet_dropout_abi_version() != DROPOUT_ABI_VERSION:
-            raise DanetHipError('libdanet_dropout_hip.so ABI version mismatch')
-        _dropout = lib
-    return _dropout
-
-
-def dropout_check(rc):
-    if rc != 0:
-        msg = load_dropout().danet_dropout_last_error()
-        raise DanetHipError('libdanet_dropout_hip error %d: %s' % (rc, msg.decode() if msg else '?'))
-
-
-# ---- the dataset front-end extension library (include/danet_prep_hip.h) ----
-# Loaded at the first use of the `wavdir` dataset (ops.stft_batch) only: a run with any other
-# DATASET_TYPE never maps it.
-PREP_LIB_PATH = os.path.join(_HERE, 'csrc', 'libdanet_prep_hip.so')
-PREP_ABI_VERSION = 1
 # name -> (restype, argtypes); mirrors include/danet_prep_hip.h
 PREP_PROTOTYPES = {
     'danet_prep_abi_version': (c_int, []),
@@ -278,44 +153,7 @@ PREP_PROTOTYPES = {
     'danet_prep_stft_batch': (c_int, [c_p, c_int, c_p, c_i64, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p,
                                       c_p, c_i64]),
 }
-_prep = None
 
-
-def load_prep():
-    '''dlopen libdanet_prep_hip.so (after torch)'''
-    global _prep
-    if _prep is not None:
-        return _prep
-    with _lock:
-        if _prep is not None:
-            return _prep
-        if not os.path.exists(PREP_LIB_PATH):
-            raise DanetHipError(
-                'libdanet_prep_hip.so not found at %s -- the wavdir dataset needs the HIP '
-                'extension library (there is no CPU fallback); build it with '
-                '`python -c "import __graft_entry__ as g; g.build()"`' % PREP_LIB_PATH)
-        lib = ctypes.CDLL(PREP_LIB_PATH, mode=ctypes.RTLD_LOCAL)
-        for name, (res, args) in PREP_PROTOTYPES.items():
-            fn = getattr(lib, name)      # AttributeError if the symbol is missing
-            fn.restype = res
-            fn.argtypes = args
-        if lib.danet_prep_abi_version() != PREP_ABI_VERSION:
-            raise DanetHipError('libdanet_prep_hip.so ABI version mismatch')
-        _prep = lib
-    return _prep
-
-
-def prep_check(rc):
-    if rc != 0:
-        msg = load_prep().danet_prep_last_error()
-        raise DanetHipError('libdanet_prep_hip error %d: %s' % (rc, msg.decode() if msg else '?'))
-
-
-# ---- the mixture level extension library (include/danet_mix_hip.h) ----
-# Loaded at the first wavdir batch with MIX_SNR_RANGE or MIX_LEVEL_RANGE set only (ops.mix_power /
-# ops.mix_scale_): a run with both keys null never maps it.
-MIX_LIB_PATH = os.path.join(_HERE, 'csrc', 'libdanet_mix_hip.so')
-MIX_ABI_VERSION = 1
 # name -> (restype, argtypes); mirrors include/danet_mix_hip.h
 MIX_PROTOTYPES = {
     'danet_mix_abi_version': (c_int, []),
@@ -324,37 +162,140 @@ MIX_PROTOTYPES = {
     'danet_mix_power': (c_int, [c_p, c_int, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_sz]),
     'danet_mix_scale_c64': (c_int, [c_p, c_int, c_int, c_int, c_p, c_i64, c_p]),
 }
-_mix = None
+
+# ---- the libraries -------------------------------------------------------------
+# Five shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# table stays exactly the core header's).  A missing library is a hard error for every one of them.
+# To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
+# exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.
+#   name: '' for the core; so: the file under csrc/; path_var / handle_var: the module globals that hold
+#   its path (read when it is loaded: tests and tools assign to it) and its CDLL (None until then);
+#   prefix: danet_<p>abi_version and danet_<p>last_error follow from it; needs: who needs it, for the
+#   message of a missing file
+Library = collections.namedtuple('Library', 'name so path_var handle_var prototypes abi prefix needs')
+CONV_ABI_VERSION = DROPOUT_ABI_VERSION = PREP_ABI_VERSION = MIX_ABI_VERSION = 1
+
+CORE = Library('', 'libdanet_hip.so', 'LIB_PATH', '_lib', PROTOTYPES, 7, 'danet_',
+               'the HIP extension is required')
+CONV = Library('conv', 'libdanet_conv_hip.so', 'CONV_LIB_PATH', '_conv', CONV_PROTOTYPES, CONV_ABI_VERSION,
+               'danet_conv_', 'the conv-bilstm-v1 encoder needs the HIP extension library')
+# loaded at the first call with keep < 1 only: a run with DROPOUT_KEEP_PROB = 1 never maps it
+DROPOUT = Library('dropout', 'libdanet_dropout_hip.so', 'DROPOUT_LIB_PATH', '_dropout', DROPOUT_PROTOTYPES,
+                  DROPOUT_ABI_VERSION, 'danet_dropout_', 'DROPOUT_KEEP_PROB < 1 needs the HIP extension library')
+# loaded at the first use of the `wavdir` dataset (ops.stft_batch) only: a run with any other DATASET_TYPE
+# never maps it
+PREP = Library('prep', 'libdanet_prep_hip.so', 'PREP_LIB_PATH', '_prep', PREP_PROTOTYPES, PREP_ABI_VERSION,
+               'danet_prep_', 'the wavdir dataset needs the HIP extension library')
+# loaded at the first wavdir batch with MIX_SNR_RANGE or MIX_LEVEL_RANGE set only (ops.mix_power /
+# ops.mix_scale_): a run with both keys null never maps it
+MIX = Library('mix', 'libdanet_mix_hip.so', 'MIX_LIB_PATH', '_mix', MIX_PROTOTYPES, MIX_ABI_VERSION,
+              'danet_mix_', 'MIX_SNR_RANGE / MIX_LEVEL_RANGE need the HIP extension library')
+LIBRARIES = (CORE, CONV, DROPOUT, PREP, MIX)
+
+# DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
+LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
+CONV_LIB_PATH = os.path.join(_CSRC, CONV.so)
+DROPOUT_LIB_PATH = os.path.join(_CSRC, DROPOUT.so)
+PREP_LIB_PATH = os.path.join(_CSRC, PREP.so)
+MIX_LIB_PATH = os.path.join(_CSRC, MIX.so)
+_lib = _conv = _dropout = _prep = _mix = None
+_lock = threading.Lock()
+
+
+class DanetHipError(RuntimeError):
+    pass
+
+
+def _load(spec, loaded=None):
+    '''dlopen the library of `spec` (after torch, so both share ONE libamdhip64), bind its prototype
+    table, check its ABI version and store the handle in its module global; then call `loaded`'''
+    g = globals()
+    if g[spec.handle_var] is None:
+        with _lock:
+            if g[spec.handle_var] is None:
+                path = g[spec.path_var]
+                if not os.path.exists(path):
+                    raise DanetHipError(
+                        '%s not found at %s -- %s (there is no CPU fallback); build it with '
+                        '`python -c "import __graft_entry__ as g; g.build()"`' % (spec.so, path, spec.needs))
+                # torch already mapped its bundled libamdhip64.so (SONAME libamdhip64.so.7);
+                # our DT_NEEDED of the same SONAME resolves to that copy.
+                lib = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
+                for name, (res, args) in spec.prototypes.items():
+                    fn = getattr(lib, name)      # AttributeError if the symbol is missing
+                    fn.restype = res
+                    fn.argtypes = args
+                if getattr(lib, spec.prefix + 'abi_version')() != spec.abi:
+                    raise DanetHipError('%s ABI version mismatch' % spec.so)
+                g[spec.handle_var] = lib
+                if loaded is not None:
+                    loaded()
+    return g[spec.handle_var]
+
+
+def _check(spec, rc):
+    '''raise the error behind the return code `rc` != 0 of a call into the library of `spec`'''
+    msg = getattr(_load(spec), spec.prefix + 'last_error')()
+    raise DanetHipError('%s error %d: %s' % (spec.so[:-3], rc, msg.decode() if msg else '?'))
+
+
+# Every load_*() answers from its global once that is set: load() runs at every kernel launch.
+def load():
+    if _lib is not None:
+        return _lib
+    return _load(CORE, apply_env_options)
+
+
+def load_conv():
+    if _conv is not None:
+        return _conv
+    return _load(CONV)
+
+
+def conv_check(rc):
+    if rc != 0:
+        _check(CONV, rc)
+
+
+def conv_ws_bytes(op, desc):
+    '''danet_conv_workspace_bytes(op, desc)'''
+    n = load_conv().danet_conv_workspace_bytes(op, ctypes.byref(desc))
+    if n == ctypes.c_size_t(-1).value:
+        conv_check(-1)
+    return n
+
+
+def load_dropout():
+    if _dropout is not None:
+        return _dropout
+    return _load(DROPOUT)
+
+
+def dropout_check(rc):
+    if rc != 0:
+        _check(DROPOUT, rc)
+
+
+def load_prep():
+    if _prep is not None:
+        return _prep
+    return _load(PREP)
+
+
+def prep_check(rc):
+    if rc != 0:
+        _check(PREP, rc)
 
 
 def load_mix():
-    '''dlopen libdanet_mix_hip.so (after torch)'''
-    global _mix
     if _mix is not None:
         return _mix
-    with _lock:
-        if _mix is not None:
-            return _mix
-        if not os.path.exists(MIX_LIB_PATH):
-            raise DanetHipError(
-                'libdanet_mix_hip.so not found at %s -- MIX_SNR_RANGE / MIX_LEVEL_RANGE need the HIP '
-                'extension library (there is no CPU fallback); build it with '
-                '`python -c "import __graft_entry__ as g; g.build()"`' % MIX_LIB_PATH)
-        lib = ctypes.CDLL(MIX_LIB_PATH, mode=ctypes.RTLD_LOCAL)
-        for name, (res, args) in MIX_PROTOTYPES.items():
-            fn = getattr(lib, name)      # AttributeError if the symbol is missing
-            fn.restype = res
-            fn.argtypes = args
-        if lib.danet_mix_abi_version() != MIX_ABI_VERSION:
-            raise DanetHipError('libdanet_mix_hip.so ABI version mismatch')
-        _mix = lib
-    return _mix
+    return _load(MIX)
 
 
 def mix_check(rc):
     if rc != 0:
-        msg = load_mix().danet_mix_last_error()
-        raise DanetHipError('libdanet_mix_hip error %d: %s' % (rc, msg.decode() if msg else '?'))
+        _check(MIX, rc)
 
 
 # ---- switches ------------------------------------------------------------------
@@ -432,9 +373,7 @@ def get_option(name):
 
 def check(rc):
     if rc != 0:
-        msg = load().danet_last_error()
-        raise DanetHipError('libdanet_hip error %d: %s' % (
-            rc, msg.decode() if msg else '?'))
+        _check(CORE, rc)
 
 
 # DANET_WS_* (include/danet_hip.h)
