@@ -1,5 +1,5 @@
 '''
-Builds the five HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the six HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -9,6 +9,7 @@ Builds the five HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_dropout_hip.so       csrc/dropout/*.hip       include/danet_dropout_hip.h
     libdanet_prep_hip.so          csrc/prep/*.hip          include/danet_prep_hip.h
     libdanet_mix_hip.so           csrc/mix/*.hip           include/danet_mix_hip.h
+    libdanet_speed_hip.so         csrc/speed/*.hip         include/danet_speed_hip.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -48,8 +49,10 @@ CONV = _extension('conv', os.path.join(CSRC, 'conv', '*.h'))
 DROPOUT = _extension('dropout')
 PREP = _extension('prep')
 MIX = _extension('mix')
-LIBRARIES = (CORE, CONV, DROPOUT, PREP, MIX)      # build() builds them in this order
-LIB, CONV_LIB, DROPOUT_LIB, PREP_LIB, MIX_LIB = (spec.out for spec in LIBRARIES)
+SPEED = _extension('speed')
+# build() builds them in this order; a new record is APPENDED (the first five are indexed by position)
+LIBRARIES = (CORE, CONV, DROPOUT, PREP, MIX, SPEED)
+LIB, CONV_LIB, DROPOUT_LIB, PREP_LIB, MIX_LIB, SPEED_LIB = (spec.out for spec in LIBRARIES)
 
 
 def _sources(src_dir):
@@ -120,6 +123,10 @@ def build_prep(force=False, verbose=True):
 
 def build_mix(force=False, verbose=True):
     return _build_library(MIX, force, verbose)
+
+
+def build_speed(force=False, verbose=True):
+    return _build_library(SPEED, force, verbose)
 
 
 def build_variant(name, defs):

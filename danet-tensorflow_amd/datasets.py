@@ -4,8 +4,9 @@ Datasets.  Only the reference's data-free `toy` generator
 corpora and are out of scope.  `synth` is the speech-shaped 8 kHz
 2-speaker generator the benchmarks use.  `wavdir` trains on a folder of the user's
 own WAV files: waveforms resident in device memory, every batch one launch of the ragged-batch
-STFT kernel (include/danet_prep_hip.h), and -- with MIX_SNR_RANGE / MIX_LEVEL_RANGE set -- one launch that
-applies the drawn per-utterance gains (include/danet_mix_hip.h).
+STFT kernel (include/danet_prep_hip.h), -- with MIX_SNR_RANGE / MIX_LEVEL_RANGE set -- one launch that
+applies the drawn per-utterance gains (include/danet_mix_hip.h) and -- with SPEED_PERTURB_RANGE set -- one
+launch in front of the STFT that resamples every train utterance by its drawn speed (include/danet_speed_hip.h).
 '''
 import os
 import random
@@ -168,7 +169,17 @@ class WavDirData(Dataset):
     at most R; the group shifted by one draw from U(-L, L)) and ONE more launch applies them to the batch the
     STFT kernel wrote (ops.mix_scale_); the gains ride in the pinned ring behind the descriptor table.  Draws
     come from a RandomState of the dataset's own per subset, seeded by (dist.shard_seed(1337), subset index):
-    `train` runs on across epochs, `valid` / `test` are re-seeded at the start of every sweep.'''
+    `train` runs on across epochs, `valid` / `test` are re-seeded at the start of every sweep.
+
+    SPEED PERTURBATION (hparams.SPEED_PERTURB_RANGE = P, 0 <= P <= 0.25, default None = off: no launch, no
+    allocation, no draw, libdanet_speed_hip.so not mapped).  `train` only: every utterance of every train batch
+    draws a speed p / 512 (plan_speed, the rule include/danet_speed_hip.h writes out) from a third RandomState,
+    seeded by (dist.shard_seed(1337), subset index, 1), BEFORE the batch's pads and crop are planned; the plan
+    then sees the new lengths L'.  ONE more launch (ops.speed_resample) writes the resampled batch from the
+    resident pool into one of DESC_DEPTH scratch waveform buffers (utterance u at u * stride, stride the longest
+    possible L' of the subset rounded up to a multiple of 4), and the STFT kernel reads that scratch; the speed
+    descriptors ride in the pinned ring between the STFT descriptors and the gains.  With MIX_SNR_RANGE the
+    powers stay those of the stored files.'''
     SUBSETS = ('train', 'valid', 'test')
     DESC_DEPTH = 8        # pinned descriptor tables in flight
     OUT_DEPTH = 3         # output buffers: a yielded batch stays valid while the next two are drawn
@@ -181,6 +192,8 @@ class WavDirData(Dataset):
         self.mix_snr_range = self.mix_level_range = None      # read from hparams by load_host
         self.power = {}             # subset -> float64 mean power sum(x^2) / len of every utterance
         self._mix_rng = {}
+        self.speed_range = None     # read from hparams by load_host
+        self._speed_rng, self._speed_table, self._speed_scratch = {}, {}, {}
         self._alias = False
 
     # ---- host half -------------------------------------------------------------------------------
@@ -223,9 +236,21 @@ class WavDirData(Dataset):
     def mix_on(self):
         return self.mix_snr_range is not None or self.mix_level_range is not None
 
+    @staticmethod
+    def speed_perturb_range():
+        '''SPEED_PERTURB_RANGE as a float or None; anything but null or a number in [0, 0.25] is a ValueError
+        that names the key'''
+        v = getattr(hparams, 'SPEED_PERTURB_RANGE', None)
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 0.25:
+                raise ValueError('hparams.SPEED_PERTURB_RANGE must be null or a number in [0, 0.25], got %r' % (v,))
+            v = float(v)
+        return v
+
     def load_host(self, out=None):
         '''discover, decode and resample every subset into host pools (no device involved)'''
         self.mix_snr_range, self.mix_level_range = self.mix_ranges()
+        self.speed_range = self.speed_perturb_range()
         root = hparams.DATASET_DIR
         if root is None:
             raise ValueError('the wavdir dataset needs hparams.DATASET_DIR: the folder that holds '
@@ -273,11 +298,12 @@ class WavDirData(Dataset):
             np.random.shuffle(indices)
         return indices.reshape(-1, batch_size)
 
-    def plan_batch(self, subset, idx, crop_len=None, crop=False):
+    def plan_batch(self, subset, idx, crop_len=None, crop=False, frames=None):
         '''(T_max, pad_left per utterance, t_begin, t_count) of one batch; draws from python's `random`
         exactly as utils.random_zeropad does per utterance (no draw for a full-length one) and then,
-        with crop=True, as feed.to_batch_host does for the crop'''
-        T = self.frames[subset][idx]
+        with crop=True, as feed.to_batch_host does for the crop.  frames: the batch's frame counts when
+        they are not the stored files' (speed perturbation)'''
+        T = self.frames[subset][idx] if frames is None else frames
         T_max = int(T.max())
         pads = [random.randint(0, T_max - int(t)) if T_max > int(t) else 0 for t in T]
         beg, cnt = 0, T_max
@@ -310,6 +336,32 @@ class WavDirData(Dataset):
             gains = np.sqrt(G / safe) * gains
         return np.where(live, gains, 1.0).reshape(-1).astype(np.float32)
 
+    # ---- speed perturbation: the draw (host, no device; include/danet_speed_hip.h) -------------------------
+    @staticmethod
+    def plan_speed(lengths, rng, P, fft_size):
+        '''(p, L') of one batch, two int64 vectors: ONE rng.uniform call draws u ~ U(-P, P) per utterance,
+        p = Q + rint(Q u) clipped to Q -+ floor(Q P), L' = floor((L - 1) Q / p) + 1; an utterance whose L'
+        would fall below fft_size keeps p = Q'''
+        from . import ops
+        Q = ops.SPEED_PHASES
+        lengths = np.asarray(lengths, dtype=np.int64)
+        k = int(np.floor(Q * P))
+        u = rng.uniform(-P, P, size=len(lengths))
+        p = np.clip(Q + np.rint(Q * u).astype(np.int64), Q - k, Q + k)
+        p[ops.speed_out_len(lengths, p) < fft_size] = Q
+        return p, ops.speed_out_len(lengths, p)
+
+    def speed_stream(self, subset):
+        '''the RandomState the train speeds are drawn from, created once (None with the key null and for
+        `valid` / `test`, which are never perturbed)'''
+        if self.speed_range is None or subset != 'train':
+            return None
+        if subset not in self._speed_rng:
+            from . import dist
+            self._speed_rng[subset] = np.random.RandomState(
+                [dist.shard_seed(1337), self.SUBSETS.index(subset), 1])
+        return self._speed_rng[subset]
+
     def _pool_key(self, subset):
         return 'test' if (subset == 'valid' and self._alias) else subset
 
@@ -326,19 +378,32 @@ class WavDirData(Dataset):
     def plan_epoch(self, subset, batch_size, shuffle=False, crop_len=None, crop=False):
         '''the host plan of one epoch, per batch (idx, T_max, pads, t_begin, t_count, gains): plan_indices, then
         per batch plan_batch and -- with a MIX_* key set -- plan_gains on self.power (else gains is None and
-        nothing is drawn).  `random` / `np.random` advance exactly as without the keys.'''
+        nothing is drawn).  `random` / `np.random` advance exactly as without the keys.  With
+        SPEED_PERTURB_RANGE set the train plan is the one of the drawn lengths (plan_epoch_speed).'''
+        for item in self.plan_epoch_speed(subset, batch_size, shuffle, crop_len, crop):
+            yield item[:6]
+
+    def plan_epoch_speed(self, subset, batch_size, shuffle=False, crop_len=None, crop=False):
+        '''plan_epoch with a seventh field: None, or -- `train` with SPEED_PERTURB_RANGE set -- the (p, L') of
+        plan_speed, drawn per batch before plan_batch, which then plans the frames of the new lengths'''
         rng = self.mix_stream(subset)
+        speed_rng = self.speed_stream(subset)
         C = hparams.MAX_N_SIGNAL
         if rng is not None and batch_size % C:
             raise ValueError('wavdir: with MIX_SNR_RANGE / MIX_LEVEL_RANGE set the batch size must be a multiple '
                              'of MAX_N_SIGNAL = %d (got %d): gains are drawn per group of sources' % (C, batch_size))
         for idx in self.plan_indices(subset, batch_size, shuffle):
-            T_max, pads, beg, cnt = self.plan_batch(subset, idx, crop_len, crop)
+            speed = frames = None
+            if speed_rng is not None:
+                speed = self.plan_speed(self.lengths[subset][idx], speed_rng, self.speed_range, hparams.FFT_SIZE)
+                frames = np.asarray([_stft_frames(int(n), hparams.FFT_SIZE, hparams.FFT_STRIDE) for n in speed[1]],
+                                    dtype=np.int64)
+            T_max, pads, beg, cnt = self.plan_batch(subset, idx, crop_len, crop, frames)
             gains = None
             if rng is not None:
                 gains = self.plan_gains(self.power[self._pool_key(subset)][idx], rng, C,
                                         self.mix_snr_range, self.mix_level_range)
-            yield idx, T_max, pads, beg, cnt, gains
+            yield idx, T_max, pads, beg, cnt, gains, speed
 
     # ---- device half -----------------------------------------------------------------------------
     @staticmethod
@@ -369,6 +434,36 @@ class WavDirData(Dataset):
             table = self.power[key] = sums / self.lengths[subset].astype(np.float64)
         return table
 
+    def speed_table_on(self, device):
+        '''the filter table of the key's P on `device` (float64 numpy rounded once, uploaded once per dataset)'''
+        t = self._speed_table.get(str(device))
+        if t is None:
+            import torch
+            from . import ops
+            t = self._speed_table[str(device)] = torch.from_numpy(ops.speed_table(self.speed_range)).to(device)
+        return t
+
+    def speed_stride(self, subset):
+        '''floats between two utterances of a scratch waveform buffer: the longest L' any draw can give the
+        subset's longest file (at most max L / (1 - P) + 1), rounded up to a multiple of 4'''
+        from . import ops
+        p_min = ops.SPEED_PHASES - int(np.floor(ops.SPEED_PHASES * self.speed_range))
+        return (int(ops.speed_out_len(int(self.lengths[subset].max()), p_min)) + 3) & ~3
+
+    def _take_scratch(self, device, subset, n_utt):
+        '''the next of DESC_DEPTH scratch waveform buffers of the subset (allocated once; as deep as the
+        descriptor ring: batches are built ahead of their consumer) -> (float32 device vector, stride)'''
+        import torch
+        key = (subset, str(device))
+        ring = self._speed_scratch.get(key)
+        if ring is None or ring['n_utt'] < n_utt:
+            stride = self.speed_stride(subset)
+            ring = self._speed_scratch[key] = dict(
+                n_utt=n_utt, stride=stride, k=0,
+                bufs=[torch.empty(n_utt * stride, dtype=torch.float32, device=device) for _ in range(self.DESC_DEPTH)])
+        ring['k'] += 1
+        return ring['bufs'][(ring['k'] - 1) % self.DESC_DEPTH], ring['stride']
+
     def _window_on(self, device):
         import torch
         w = self._window.get(str(device))
@@ -388,10 +483,16 @@ class WavDirData(Dataset):
         pool, window = self.upload_pool(subset, device), self._window_on(device)
         if self.mix_on:
             self.power_table(subset, pool)
-        for idx, T_max, pads, _beg, _cnt, gains in self.plan_epoch(subset, batch_size, shuffle):
-            desc = ops.prep_desc(self.offsets[subset][idx], self.lengths[subset][idx], pads, T_max,
-                                 pool.numel(), hparams.FFT_SIZE, hparams.FFT_STRIDE)
-            spectra = ops.stft_batch(pool, desc, T_max, window, hparams.FFT_SIZE, hparams.FFT_STRIDE,
+        for idx, T_max, pads, _beg, _cnt, gains, speed in self.plan_epoch_speed(subset, batch_size, shuffle):
+            src, offsets, lengths = pool, self.offsets[subset][idx], self.lengths[subset][idx]
+            if speed is not None:         # resampled into a scratch buffer the STFT then reads
+                src, stride = self._take_scratch(device, subset, batch_size)
+                spots = np.arange(len(idx), dtype=np.int64) * stride
+                ops.speed_resample(pool, ops.speed_desc(offsets, lengths, spots, speed[1], speed[0], pool.numel(),
+                                                        src.numel()), self.speed_table_on(device), src)
+                offsets, lengths = spots, speed[1]
+            desc = ops.prep_desc(offsets, lengths, pads, T_max, src.numel(), hparams.FFT_SIZE, hparams.FFT_STRIDE)
+            spectra = ops.stft_batch(src, desc, T_max, window, hparams.FFT_SIZE, hparams.FFT_STRIDE,
                                      t_begin=0, t_count=T_max)
             if gains is not None:
                 ops.mix_scale_(spectra, torch.from_numpy(gains).to(device))
@@ -401,6 +502,8 @@ class WavDirData(Dataset):
         import torch
         from . import ops
         row = ops.PREP_DESC_DTYPE.itemsize + (4 if self.mix_on else 0)      # + one float32 gain
+        if self.speed_range is not None:
+            row += ops.SPEED_DESC_DTYPE.itemsize                            # + one speed descriptor
         ring = self._ring.get(str(device))
         if ring is None or ring['n_utt'] < n_utt or ring['row'] < row:
             slots = []
@@ -432,16 +535,20 @@ class WavDirData(Dataset):
         if self.mix_on:
             self.power_table(subset, pool)
         ring = self._take_ring(device, batch_size)
-        for idx, T_max, pads, beg, cnt, gains in self.plan_epoch(subset, batch_size, shuffle, crop_len, crop=True):
-            if gains is None:
-                out = self._emit(device, pool, window, ring, subset, idx, T_max, pads, beg, cnt)
-            else:
-                out = self._emit(device, pool, window, ring, subset, idx, T_max, pads, beg, cnt, gains=gains)
+        for idx, T_max, pads, beg, cnt, gains, speed in self.plan_epoch_speed(subset, batch_size, shuffle, crop_len,
+                                                                              crop=True):
+            more = {}
+            if gains is not None:
+                more['gains'] = gains
+            if speed is not None:
+                more['speed'] = speed
+            out = self._emit(device, pool, window, ring, subset, idx, T_max, pads, beg, cnt, **more)
             yield out.view(B, C, cnt, F)
 
-    def _emit(self, device, pool, window, ring, subset, idx, T_max, pads, beg, cnt, gains=None):
-        '''the device half of one batch: descriptor table (and the gains behind it, in the same copy) through
-        the pinned ring, one launch into the next output buffer (and one that scales it in place)
+    def _emit(self, device, pool, window, ring, subset, idx, T_max, pads, beg, cnt, gains=None, speed=None):
+        '''the device half of one batch: descriptor table (and the speed descriptors and the gains behind it,
+        in the same copy) through the pinned ring, (one launch that resamples the batch into a scratch
+        waveform buffer,) one launch into the next output buffer (and one that scales it in place)
         -> complex64 [batch, cnt, F]'''
         import torch
         from . import ops
@@ -453,12 +560,20 @@ class WavDirData(Dataset):
         if slot.used:
             slot.event.synchronize()      # the copy out of this table DESC_DEPTH batches ago: long done
         table = slot.pin[:batch_size * row].numpy().view(ops.PREP_DESC_DTYPE)
-        ops.prep_desc(self.offsets[subset][idx], self.lengths[subset][idx], pads, T_max,
-                      pool.numel(), N, S, out=table)
         dev_table, sent = slot.dev[:batch_size * row], batch_size * row
-        if gains is not None:             # float32 [batch] right behind the table: one copy carries both
-            sent += batch_size * 4
-            slot.pin[batch_size * row:sent].numpy().view(np.float32)[:] = gains
+        src, offsets, lengths = pool, self.offsets[subset][idx], self.lengths[subset][idx]
+        if speed is not None:             # 40-byte rows right behind the table: the scratch the STFT then reads
+            src, stride = self._take_scratch(device, subset, batch_size)
+            spots = np.arange(batch_size, dtype=np.int64) * stride
+            at, sent = sent, sent + batch_size * ops.SPEED_DESC_DTYPE.itemsize
+            ops.speed_desc(offsets, lengths, spots, speed[1], speed[0], pool.numel(), src.numel(),
+                           out=slot.pin[at:sent].numpy().view(ops.SPEED_DESC_DTYPE))
+            dev_speed, offsets, lengths = slot.dev[at:sent], spots, speed[1]
+        ops.prep_desc(offsets, lengths, pads, T_max, src.numel(), N, S, out=table)
+        if gains is not None:             # float32 [batch] behind the descriptors: one copy carries them all
+            at, sent = sent, sent + batch_size * 4
+            slot.pin[at:sent].numpy().view(np.float32)[:] = gains
+            dev_gains = slot.dev[at:sent].view(torch.float32)
         slot.dev[:sent].copy_(slot.pin[:sent], non_blocking=True)
         slot.event.record(torch.cuda.current_stream(device))
         slot.used = True
@@ -467,7 +582,9 @@ class WavDirData(Dataset):
         if buf is None or buf.numel() < n:
             buf = ring['out'][k % self.OUT_DEPTH] = torch.empty(n, dtype=torch.complex64, device=device)
         out = buf[:n].view(batch_size, cnt, F)
-        ops.stft_batch(pool, dev_table, T_max, window, N, S, t_begin=beg, t_count=cnt, out=out)
+        if speed is not None:
+            ops.speed_resample(pool, dev_speed, self.speed_table_on(device), src)
+        ops.stft_batch(src, dev_table, T_max, window, N, S, t_begin=beg, t_count=cnt, out=out)
         if gains is not None:
-            ops.mix_scale_(out, slot.dev[batch_size * row:sent].view(torch.float32))
+            ops.mix_scale_(out, dev_gains)
         return out

@@ -21,6 +21,8 @@ unchanged.  Differences, all deliberate:
 * `MIX_SNR_RANGE` / `MIX_LEVEL_RANGE` (dB, default None = off) make the `wavdir` dataset mix
   its sources at a drawn relative level / shift the whole mixture by a drawn level
   (the reference's `# TODO add mixing coeff ?`, `main.py:230`); every other dataset ignores them.
+* `SPEED_PERTURB_RANGE` (a fraction in [0, 0.25], default None = off) makes the `wavdir` dataset
+  resample every utterance of every train batch by a drawn speed factor; every other dataset ignores it.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -74,6 +76,9 @@ DEFAULTS = {
     # mixture level control of the `wavdir` dataset, dB, None = off (not in the reference; include/danet_mix_hip.h)
     'MIX_SNR_RANGE': None,
     'MIX_LEVEL_RANGE': None,
+    # speed perturbation of the `wavdir` dataset's train subset, a fraction in [0, 0.25], None = off (not in the
+    # reference; include/danet_speed_hip.h)
+    'SPEED_PERTURB_RANGE': None,
 }
 
 

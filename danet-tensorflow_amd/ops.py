@@ -527,6 +527,90 @@ def mix_scale_(batch, gains):
     return batch
 
 
+# ---- speed perturbation of the wavdir dataset (include/danet_speed_hip.h) ----------------------------
+# On the extension library libdanet_speed_hip.so, mapped at the first call: a wavdir run with
+# SPEED_PERTURB_RANGE null never gets here.
+SPEED_PHASES, SPEED_TAPS = 512, 32                   # Q, 2Z (DANET_SPEED_PHASES, DANET_SPEED_TAPS)
+SPEED_P_MIN, SPEED_P_MAX = SPEED_PHASES - SPEED_PHASES // 4, SPEED_PHASES + SPEED_PHASES // 4
+SPEED_DESC_DTYPE = np.dtype([('src_offset', '<i8'), ('src_length', '<i8'), ('dst_offset', '<i8'),
+                             ('dst_length', '<i8'), ('p', '<i4'), ('reserved', '<i4')])
+
+
+def speed_table(P):
+    '''the float32 [Q][2Z] filter table of SPEED_PERTURB_RANGE = P (the rule of include/danet_speed_hip.h):
+    float64 numpy, rounded once.  Host only, no library involved.'''
+    Q, Z = SPEED_PHASES, SPEED_TAPS // 2
+    fc = 1.0 / (1.0 + float(P))
+    t = (np.arange(2 * Z, dtype=np.float64)[None, :] - (Z - 1)) - np.arange(Q, dtype=np.float64)[:, None] / Q
+    a = fc * t
+    k = np.rint(a)                                       # sin(pi a) = (-1)^k sin(pi (a - k)): exactly 0 at an integer a
+    s = np.where(k % 2 == 0, 1.0, -1.0) * np.sin(np.pi * (a - k))
+    sinc = np.where(a == 0, 1.0, s / np.where(a == 0, 1.0, np.pi * a))
+    h = fc * sinc * 0.5 * (1.0 + np.cos(np.pi * t / Z))
+    return (np.where(np.abs(t) < Z, h, 0.0) + 0.0).astype(np.float32)       # + 0.0: a zero tap is +0
+
+
+def speed_out_len(L, p):
+    '''L' = floor((L - 1) * Q / p) + 1 for an array of lengths and of speed numerators (int64 numpy; the rule
+    danet_speed_out_len applies).  Host only, no library involved.'''
+    L, p = np.asarray(L, dtype=np.int64), np.asarray(p, dtype=np.int64)
+    return (L - 1) * SPEED_PHASES // p + 1
+
+
+def speed_desc(src_offsets, src_lengths, dst_offsets, dst_lengths, p, src_len, dst_len, out=None):
+    '''the validated descriptor table of one launch as a numpy record array (SPEED_DESC_DTYPE; into `out`
+    when given).  Everything the kernel would have to clamp is a ValueError HERE, before any upload or
+    launch: a source span outside the pool, a destination span outside the buffer or across another, a p
+    outside [SPEED_P_MIN, SPEED_P_MAX].'''
+    n = len(src_offsets)
+    d = np.zeros(n, SPEED_DESC_DTYPE) if out is None else out
+    assert d.dtype == SPEED_DESC_DTYPE and d.shape == (n,)
+    d['src_offset'], d['src_length'], d['dst_offset'], d['dst_length'] = src_offsets, src_lengths, dst_offsets, dst_lengths
+    d['p'], d['reserved'] = p, 0
+    so, sl, do, dl, pp = (d[k].astype(np.int64) for k in ('src_offset', 'src_length', 'dst_offset', 'dst_length', 'p'))
+    bad = np.nonzero((so < 0) | (sl < 1) | (so + sl > src_len))[0]
+    if len(bad):
+        u = int(bad[0])
+        raise ValueError('speed_resample: utterance %d [%d, %d) is outside the pool of %d samples'
+                         % (u, so[u], so[u] + sl[u], src_len))
+    bad = np.nonzero((pp < SPEED_P_MIN) | (pp > SPEED_P_MAX))[0]
+    if len(bad):
+        raise ValueError('speed_resample: utterance %d: p = %d is outside [%d, %d]'
+                         % (bad[0], pp[bad[0]], SPEED_P_MIN, SPEED_P_MAX))
+    order = np.argsort(do, kind='stable')
+    bad = np.nonzero((do < 0) | (dl < 0) | (do + dl > dst_len))[0]
+    if len(bad) or np.any(do[order][1:] < (do + dl)[order][:-1]):
+        raise ValueError('speed_resample: the destination spans must lie inside the buffer of %d samples and '
+                         'apart from each other' % dst_len)
+    return d
+
+
+def speed_resample(pool, desc, table, out):
+    '''every utterance `desc` describes resampled from the float32 device vector `pool` into the float32
+    device vector `out`, ONE launch (danet_speed_resample); nothing of `out` outside the destination spans
+    is touched.  desc: the table of ops.speed_desc -- a numpy record array (validated again and uploaded
+    here) or a device uint8 / int64 tensor of 40-byte rows the caller has validated and uploaded.
+    table: ops.speed_table(P) on the device, float32 [512, 32].  There is no CPU fallback.'''
+    for t in (pool, out):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()
+    assert table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()
+    assert tuple(table.shape) == (SPEED_PHASES, SPEED_TAPS) and table.device == pool.device == out.device
+    if not torch.is_tensor(desc):
+        desc = np.asarray(desc)
+        if desc.dtype != SPEED_DESC_DTYPE:
+            raise TypeError('speed_resample: desc must be a SPEED_DESC_DTYPE record array or a device tensor')
+        speed_desc(desc['src_offset'], desc['src_length'], desc['dst_offset'], desc['dst_length'], desc['p'],
+                   pool.numel(), out.numel())
+        desc = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8).copy()).to(pool.device)
+    row = SPEED_DESC_DTYPE.itemsize
+    assert desc.is_cuda and desc.is_contiguous() and (desc.numel() * desc.element_size()) % row == 0
+    n_utt = desc.numel() * desc.element_size() // row
+    with _lib.timed('speed_resample'):
+        _lib.speed_check(_lib.load_speed().danet_speed_resample(
+            _lib.stream(), n_utt, ptr(pool), pool.numel(), ptr(desc), ptr(table), ptr(out), out.numel()))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # LSTM layer (both directions), raw forward / backward on time-major tensors
 # ---------------------------------------------------------------------------
