@@ -1,5 +1,5 @@
 '''
-Builds the six HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the seven HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -10,6 +10,7 @@ Builds the six HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_prep_hip.so          csrc/prep/*.hip          include/danet_prep_hip.h
     libdanet_mix_hip.so           csrc/mix/*.hip           include/danet_mix_hip.h
     libdanet_speed_hip.so         csrc/speed/*.hip         include/danet_speed_hip.h
+    libdanet_reverb_hip.so        csrc/reverb/*.hip        include/danet_reverb_hip.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -53,6 +54,11 @@ SPEED = _extension('speed')
 # build() builds them in this order; a new record is APPENDED (the first five are indexed by position)
 LIBRARIES = (CORE, CONV, DROPOUT, PREP, MIX, SPEED)
 LIB, CONV_LIB, DROPOUT_LIB, PREP_LIB, MIX_LIB, SPEED_LIB = (spec.out for spec in LIBRARIES)
+# LIBRARIES stays the six records above; every library added after them goes HERE, appended, and build() runs
+# over LIBRARIES + LATER_LIBRARIES
+REVERB = _extension('reverb')
+LATER_LIBRARIES = (REVERB,)
+REVERB_LIB = REVERB.out
 
 
 def _sources(src_dir):
@@ -104,7 +110,7 @@ def _build_library(spec, force, verbose):
 
 
 def build(force=False, verbose=True):
-    for spec in LIBRARIES:
+    for spec in LIBRARIES + LATER_LIBRARIES:
         _build_library(spec, force, verbose)
     return LIB
 
@@ -127,6 +133,10 @@ def build_mix(force=False, verbose=True):
 
 def build_speed(force=False, verbose=True):
     return _build_library(SPEED, force, verbose)
+
+
+def build_reverb(force=False, verbose=True):
+    return _build_library(REVERB, force, verbose)
 
 
 def build_variant(name, defs):

@@ -1,7 +1,7 @@
 '''
-ctypes binding of the six HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
-libdanet_hip.so and the conv, dropout, prep, mix and speed extension libraries.  Each is described once, by a
-record of ALL_LIBRARIES; one loader (_load) and one error check (_check) serve them all.
+ctypes binding of the seven HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+libdanet_hip.so and the conv, dropout, prep, mix, speed and reverb extension libraries.  Each is described once,
+by a record of ALL_LIBRARIES or LATER_LIBRARIES; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
 RuntimeError is raised.  PyTorch is used only to own device memory and streams;
@@ -171,19 +171,28 @@ SPEED_PROTOTYPES = {
     'danet_speed_resample': (c_int, [c_p, c_int, c_p, c_i64, c_p, c_p, c_p, c_i64]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_reverb_hip.h
+REVERB_PROTOTYPES = {
+    'danet_reverb_abi_version': (c_int, []),
+    'danet_reverb_last_error': (ctypes.c_char_p, []),
+    'danet_reverb_apply': (c_int, [c_p, c_int, c_p, c_i64, c_p, c_p, c_int, c_p, c_i64]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Six shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Seven shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
-# records the per-record tests are written against, by position; a later library is APPENDED to ALL_LIBRARIES
-# (and to _build.LIBRARIES), never inserted.
+# records the per-record tests are written against, by position, ALL_LIBRARIES those and SPEED, and
+# _build.LIBRARIES the same six; every library after them is APPENDED to LATER_LIBRARIES, here and in
+# _build.py, and is served by the same Library record type, _load, _check and _build_library.
 #   name: '' for the core; so: the file under csrc/; path_var / handle_var: the module globals that hold
 #   its path (read when it is loaded: tests and tools assign to it) and its CDLL (None until then);
 #   prefix: danet_<p>abi_version and danet_<p>last_error follow from it; needs: who needs it, for the
 #   message of a missing file
 Library = collections.namedtuple('Library', 'name so path_var handle_var prototypes abi prefix needs')
 CONV_ABI_VERSION = DROPOUT_ABI_VERSION = PREP_ABI_VERSION = MIX_ABI_VERSION = SPEED_ABI_VERSION = 1
+REVERB_ABI_VERSION = 1
 
 CORE = Library('', 'libdanet_hip.so', 'LIB_PATH', '_lib', PROTOTYPES, 7, 'danet_',
                'the HIP extension is required')
@@ -204,8 +213,13 @@ MIX = Library('mix', 'libdanet_mix_hip.so', 'MIX_LIB_PATH', '_mix', MIX_PROTOTYP
 # the key null, and every evaluation sweep, never maps it
 SPEED = Library('speed', 'libdanet_speed_hip.so', 'SPEED_LIB_PATH', '_speed', SPEED_PROTOTYPES, SPEED_ABI_VERSION,
                 'danet_speed_', 'SPEED_PERTURB_RANGE needs the HIP extension library')
+# loaded at the first wavdir TRAIN batch with REVERB_RT60_MAX set only (ops.reverb_apply): a run with the key
+# null, and every evaluation sweep, never maps it
+REVERB = Library('reverb', 'libdanet_reverb_hip.so', 'REVERB_LIB_PATH', '_reverb', REVERB_PROTOTYPES,
+                 REVERB_ABI_VERSION, 'danet_reverb_', 'REVERB_RT60_MAX needs the HIP extension library')
 LIBRARIES = (CORE, CONV, DROPOUT, PREP, MIX)
 ALL_LIBRARIES = LIBRARIES + (SPEED,)
+LATER_LIBRARIES = (REVERB,)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -214,7 +228,8 @@ DROPOUT_LIB_PATH = os.path.join(_CSRC, DROPOUT.so)
 PREP_LIB_PATH = os.path.join(_CSRC, PREP.so)
 MIX_LIB_PATH = os.path.join(_CSRC, MIX.so)
 SPEED_LIB_PATH = os.path.join(_CSRC, SPEED.so)
-_lib = _conv = _dropout = _prep = _mix = _speed = None
+REVERB_LIB_PATH = os.path.join(_CSRC, REVERB.so)
+_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = None
 _lock = threading.Lock()
 
 
@@ -323,6 +338,17 @@ def load_speed():
 def speed_check(rc):
     if rc != 0:
         _check(SPEED, rc)
+
+
+def load_reverb():
+    if _reverb is not None:
+        return _reverb
+    return _load(REVERB)
+
+
+def reverb_check(rc):
+    if rc != 0:
+        _check(REVERB, rc)
 
 
 # ---- switches ------------------------------------------------------------------

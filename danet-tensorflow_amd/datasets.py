@@ -5,8 +5,10 @@ corpora and are out of scope.  `synth` is the speech-shaped 8 kHz
 2-speaker generator the benchmarks use.  `wavdir` trains on a folder of the user's
 own WAV files: waveforms resident in device memory, every batch one launch of the ragged-batch
 STFT kernel (include/danet_prep_hip.h), -- with MIX_SNR_RANGE / MIX_LEVEL_RANGE set -- one launch that
-applies the drawn per-utterance gains (include/danet_mix_hip.h) and -- with SPEED_PERTURB_RANGE set -- one
-launch in front of the STFT that resamples every train utterance by its drawn speed (include/danet_speed_hip.h).
+applies the drawn per-utterance gains (include/danet_mix_hip.h), -- with SPEED_PERTURB_RANGE set -- one
+launch in front of the STFT that resamples every train utterance by its drawn speed (include/danet_speed_hip.h)
+and -- with REVERB_RT60_MAX set -- one launch behind that one that convolves every train utterance with its drawn
+room response (include/danet_reverb_hip.h).
 '''
 import os
 import random
@@ -179,7 +181,21 @@ class WavDirData(Dataset):
     resident pool into one of DESC_DEPTH scratch waveform buffers (utterance u at u * stride, stride the longest
     possible L' of the subset rounded up to a multiple of 4), and the STFT kernel reads that scratch; the speed
     descriptors ride in the pinned ring between the STFT descriptors and the gains.  With MIX_SNR_RANGE the
-    powers stay those of the stored files.'''
+    powers stay those of the stored files.
+
+    REVERBERATION (hparams.REVERB_RT60_MAX = R seconds, 0 <= R <= 1.0, default None = off: no launch, no
+    allocation, no draw, libdanet_reverb_hip.so not mapped).  `train` only: every utterance of every train batch
+    draws a row of a bank of 32 synthetic room responses (plan_reverb, the rule include/danet_reverb_hip.h writes
+    out; row 0 is dry) from a fourth RandomState, seeded by (dist.shard_seed(1337), subset index, 2).  The bank
+    is a property of (R, SMPRATE), the same on every rank, and is uploaded once.  ONE more launch
+    (ops.reverb_apply) convolves the batch -- from the pool, or from the speed scratch when speed is on too --
+    into one of DESC_DEPTH scratch waveform buffers of its own (filled with NaN once, when they are allocated),
+    and the STFT kernel reads that scratch.  The tail beyond an utterance's length is cut, so lengths, frames,
+    pads and crop are those without the key; the training targets are the reverberant sources.  epoch() asks for
+    whole utterances, epoch_device() only for the samples the cropped frames read (reverb_span); the kernel's
+    values do not depend on the span, so both routes give the same batches bit for bit.  The 48-byte reverb
+    descriptors ride in the pinned ring behind the speed descriptors and before the gains.  With MIX_SNR_RANGE
+    the powers stay those of the stored files.'''
     SUBSETS = ('train', 'valid', 'test')
     DESC_DEPTH = 8        # pinned descriptor tables in flight
     OUT_DEPTH = 3         # output buffers: a yielded batch stays valid while the next two are drawn
@@ -194,6 +210,8 @@ class WavDirData(Dataset):
         self._mix_rng = {}
         self.speed_range = None     # read from hparams by load_host
         self._speed_rng, self._speed_table, self._speed_scratch = {}, {}, {}
+        self.reverb_rt60 = None     # read from hparams by load_host
+        self._reverb_rng, self._reverb_bank, self._reverb_scratch = {}, {}, {}
         self._alias = False
 
     # ---- host half -------------------------------------------------------------------------------
@@ -247,10 +265,29 @@ class WavDirData(Dataset):
             v = float(v)
         return v
 
+    @staticmethod
+    def reverb_rt60_max():
+        '''REVERB_RT60_MAX as a float or None; anything but null or a number of seconds in [0, 1.0] is a
+        ValueError that names the key, and so is one whose tap count at SMPRATE exceeds the header's envelope'''
+        v = getattr(hparams, 'REVERB_RT60_MAX', None)
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 1.0:
+                raise ValueError('hparams.REVERB_RT60_MAX must be null or a number of seconds in [0, 1.0], got %r'
+                                 % (v,))
+            v = float(v)
+            from . import ops
+            K = ops.reverb_taps(v, hparams.SMPRATE)
+            if K > ops.REVERB_MAX_TAPS:
+                raise ValueError('hparams.REVERB_RT60_MAX = %r at SMPRATE = %r needs a room response of %d taps; '
+                                 'include/danet_reverb_hip.h takes at most %d' % (v, hparams.SMPRATE, K,
+                                                                                  ops.REVERB_MAX_TAPS))
+        return v
+
     def load_host(self, out=None):
         '''discover, decode and resample every subset into host pools (no device involved)'''
         self.mix_snr_range, self.mix_level_range = self.mix_ranges()
         self.speed_range = self.speed_perturb_range()
+        self.reverb_rt60 = self.reverb_rt60_max()
         root = hparams.DATASET_DIR
         if root is None:
             raise ValueError('the wavdir dataset needs hparams.DATASET_DIR: the folder that holds '
@@ -362,6 +399,41 @@ class WavDirData(Dataset):
                 [dist.shard_seed(1337), self.SUBSETS.index(subset), 1])
         return self._speed_rng[subset]
 
+    # ---- reverberation: the draw and the span (host, no device; include/danet_reverb_hip.h) ---------------
+    @staticmethod
+    def plan_reverb(n, rng):
+        '''the bank rows of one batch of n utterances, an int64 vector: ONE rng.randint(0, NB) call'''
+        from . import ops
+        return rng.randint(0, ops.REVERB_ROWS, size=n).astype(np.int64)
+
+    def reverb_stream(self, subset):
+        '''the RandomState the train rows are drawn from, created once (None with the key null and for
+        `valid` / `test`, which are never reverberated)'''
+        if self.reverb_rt60 is None or subset != 'train':
+            return None
+        if subset not in self._reverb_rng:
+            from . import dist
+            self._reverb_rng[subset] = np.random.RandomState(
+                [dist.shard_seed(1337), self.SUBSETS.index(subset), 2])
+        return self._reverb_rng[subset]
+
+    @staticmethod
+    def reverb_span(lengths, pads, beg, cnt, fft_size, fft_stride):
+        '''(out_begin, out_count) per utterance, two int64 vectors: the samples that frames [beg, beg + cnt) of
+        the padded batch read.  Utterance u's own frame t sits at pads[u] + t of the batch's axis and reads the
+        samples [t S - N / 2, t S + N / 2) (include/danet_prep_hip.h: N / 2 zeros in front of the waveform,
+        integer framing); what falls outside [0, length) is the transform's zero padding'''
+        N, S = fft_size, fft_stride
+        first, count = np.zeros(len(lengths), np.int64), np.zeros(len(lengths), np.int64)
+        for u, (L, pad) in enumerate(zip(lengths, pads)):
+            L, pad = int(L), int(pad)
+            a, b = max(beg - pad, 0), min(beg + cnt - pad, _stft_frames(L, N, S))
+            if b > a:
+                lo, hi = max(a * S - N // 2, 0), min((b - 1) * S + N // 2, L)
+                if hi > lo:
+                    first[u], count[u] = lo, hi - lo
+        return first, count
+
     def _pool_key(self, subset):
         return 'test' if (subset == 'valid' and self._alias) else subset
 
@@ -380,14 +452,21 @@ class WavDirData(Dataset):
         per batch plan_batch and -- with a MIX_* key set -- plan_gains on self.power (else gains is None and
         nothing is drawn).  `random` / `np.random` advance exactly as without the keys.  With
         SPEED_PERTURB_RANGE set the train plan is the one of the drawn lengths (plan_epoch_speed).'''
-        for item in self.plan_epoch_speed(subset, batch_size, shuffle, crop_len, crop):
+        for item in self.plan_epoch_reverb(subset, batch_size, shuffle, crop_len, crop):
             yield item[:6]
 
     def plan_epoch_speed(self, subset, batch_size, shuffle=False, crop_len=None, crop=False):
         '''plan_epoch with a seventh field: None, or -- `train` with SPEED_PERTURB_RANGE set -- the (p, L') of
         plan_speed, drawn per batch before plan_batch, which then plans the frames of the new lengths'''
+        for item in self.plan_epoch_reverb(subset, batch_size, shuffle, crop_len, crop):
+            yield item[:7]
+
+    def plan_epoch_reverb(self, subset, batch_size, shuffle=False, crop_len=None, crop=False):
+        '''plan_epoch_speed with an eighth field: None, or -- `train` with REVERB_RT60_MAX set -- the bank rows
+        of plan_reverb, drawn per batch from a stream of their own (nothing else moves)'''
         rng = self.mix_stream(subset)
         speed_rng = self.speed_stream(subset)
+        reverb_rng = self.reverb_stream(subset)
         C = hparams.MAX_N_SIGNAL
         if rng is not None and batch_size % C:
             raise ValueError('wavdir: with MIX_SNR_RANGE / MIX_LEVEL_RANGE set the batch size must be a multiple '
@@ -403,7 +482,8 @@ class WavDirData(Dataset):
             if rng is not None:
                 gains = self.plan_gains(self.power[self._pool_key(subset)][idx], rng, C,
                                         self.mix_snr_range, self.mix_level_range)
-            yield idx, T_max, pads, beg, cnt, gains, speed
+            rows = self.plan_reverb(len(idx), reverb_rng) if reverb_rng is not None else None
+            yield idx, T_max, pads, beg, cnt, gains, speed, rows
 
     # ---- device half -----------------------------------------------------------------------------
     @staticmethod
@@ -464,6 +544,34 @@ class WavDirData(Dataset):
         ring['k'] += 1
         return ring['bufs'][(ring['k'] - 1) % self.DESC_DEPTH], ring['stride']
 
+    def reverb_bank_on(self, device):
+        '''the bank of room responses of the key's R on `device` (float64 numpy rounded once, uploaded once per
+        dataset) -> float32 [32, K]'''
+        t = self._reverb_bank.get(str(device))
+        if t is None:
+            import torch
+            from . import ops
+            t = self._reverb_bank[str(device)] = torch.from_numpy(
+                ops.reverb_bank(self.reverb_rt60, hparams.SMPRATE)).to(device)
+        return t
+
+    def _take_reverb_scratch(self, device, subset, n_utt):
+        '''the next of DESC_DEPTH scratch buffers of reverberated waveforms of the subset (allocated once and
+        filled with NaN once, so that a frame that reads outside the span asked for is loud) -> (float32 device
+        vector, stride: speed's when speed is on, else the subset's longest file rounded up to a multiple of 4)'''
+        import torch
+        key = (subset, str(device))
+        ring = self._reverb_scratch.get(key)
+        if ring is None or ring['n_utt'] < n_utt:
+            stride = (self.speed_stride(subset) if self.speed_range is not None
+                      else (int(self.lengths[subset].max()) + 3) & ~3)
+            ring = self._reverb_scratch[key] = dict(
+                n_utt=n_utt, stride=stride, k=0,
+                bufs=[torch.full((n_utt * stride,), float('nan'), dtype=torch.float32, device=device)
+                      for _ in range(self.DESC_DEPTH)])
+        ring['k'] += 1
+        return ring['bufs'][(ring['k'] - 1) % self.DESC_DEPTH], ring['stride']
+
     def _window_on(self, device):
         import torch
         w = self._window.get(str(device))
@@ -483,7 +591,7 @@ class WavDirData(Dataset):
         pool, window = self.upload_pool(subset, device), self._window_on(device)
         if self.mix_on:
             self.power_table(subset, pool)
-        for idx, T_max, pads, _beg, _cnt, gains, speed in self.plan_epoch_speed(subset, batch_size, shuffle):
+        for idx, T_max, pads, _beg, _cnt, gains, speed, rows in self.plan_epoch_reverb(subset, batch_size, shuffle):
             src, offsets, lengths = pool, self.offsets[subset][idx], self.lengths[subset][idx]
             if speed is not None:         # resampled into a scratch buffer the STFT then reads
                 src, stride = self._take_scratch(device, subset, batch_size)
@@ -491,6 +599,13 @@ class WavDirData(Dataset):
                 ops.speed_resample(pool, ops.speed_desc(offsets, lengths, spots, speed[1], speed[0], pool.numel(),
                                                         src.numel()), self.speed_table_on(device), src)
                 offsets, lengths = spots, speed[1]
+            if rows is not None:          # whole utterances convolved into a scratch buffer the STFT then reads
+                dry, (src, stride) = src, self._take_reverb_scratch(device, subset, batch_size)
+                spots = np.arange(len(idx), dtype=np.int64) * stride
+                bank = self.reverb_bank_on(device)
+                ops.reverb_apply(dry, ops.reverb_desc(offsets, lengths, spots, np.zeros(len(idx), np.int64), lengths,
+                                                      rows, dry.numel(), src.numel()), bank, bank.shape[1], src)
+                offsets = spots
             desc = ops.prep_desc(offsets, lengths, pads, T_max, src.numel(), hparams.FFT_SIZE, hparams.FFT_STRIDE)
             spectra = ops.stft_batch(src, desc, T_max, window, hparams.FFT_SIZE, hparams.FFT_STRIDE,
                                      t_begin=0, t_count=T_max)
@@ -504,6 +619,8 @@ class WavDirData(Dataset):
         row = ops.PREP_DESC_DTYPE.itemsize + (4 if self.mix_on else 0)      # + one float32 gain
         if self.speed_range is not None:
             row += ops.SPEED_DESC_DTYPE.itemsize                            # + one speed descriptor
+        if self.reverb_rt60 is not None:
+            row += ops.REVERB_DESC_DTYPE.itemsize                           # + one reverb descriptor
         ring = self._ring.get(str(device))
         if ring is None or ring['n_utt'] < n_utt or ring['row'] < row:
             slots = []
@@ -535,21 +652,24 @@ class WavDirData(Dataset):
         if self.mix_on:
             self.power_table(subset, pool)
         ring = self._take_ring(device, batch_size)
-        for idx, T_max, pads, beg, cnt, gains, speed in self.plan_epoch_speed(subset, batch_size, shuffle, crop_len,
-                                                                              crop=True):
+        for idx, T_max, pads, beg, cnt, gains, speed, rows in self.plan_epoch_reverb(subset, batch_size, shuffle,
+                                                                                     crop_len, crop=True):
             more = {}
             if gains is not None:
                 more['gains'] = gains
             if speed is not None:
                 more['speed'] = speed
+            if rows is not None:
+                more['reverb'] = rows
             out = self._emit(device, pool, window, ring, subset, idx, T_max, pads, beg, cnt, **more)
             yield out.view(B, C, cnt, F)
 
-    def _emit(self, device, pool, window, ring, subset, idx, T_max, pads, beg, cnt, gains=None, speed=None):
-        '''the device half of one batch: descriptor table (and the speed descriptors and the gains behind it,
-        in the same copy) through the pinned ring, (one launch that resamples the batch into a scratch
-        waveform buffer,) one launch into the next output buffer (and one that scales it in place)
-        -> complex64 [batch, cnt, F]'''
+    def _emit(self, device, pool, window, ring, subset, idx, T_max, pads, beg, cnt, gains=None, speed=None,
+              reverb=None):
+        '''the device half of one batch: descriptor table (and the speed descriptors, the reverb descriptors and
+        the gains behind it, in the same copy) through the pinned ring, (one launch that resamples the batch into
+        a scratch waveform buffer, one that convolves the samples the cropped frames read into another,) one
+        launch into the next output buffer (and one that scales it in place) -> complex64 [batch, cnt, F]'''
         import torch
         from . import ops
         N, S, F = hparams.FFT_SIZE, hparams.FFT_STRIDE, hparams.FEATURE_SIZE
@@ -569,6 +689,14 @@ class WavDirData(Dataset):
             ops.speed_desc(offsets, lengths, spots, speed[1], speed[0], pool.numel(), src.numel(),
                            out=slot.pin[at:sent].numpy().view(ops.SPEED_DESC_DTYPE))
             dev_speed, offsets, lengths = slot.dev[at:sent], spots, speed[1]
+        if reverb is not None:            # 48-byte rows behind those: the scratch the STFT reads instead
+            dry, (src, stride) = src, self._take_reverb_scratch(device, subset, batch_size)
+            spots = np.arange(batch_size, dtype=np.int64) * stride
+            at, sent = sent, sent + batch_size * ops.REVERB_DESC_DTYPE.itemsize
+            first, count = self.reverb_span(lengths, pads, beg, cnt, N, S)
+            ops.reverb_desc(offsets, lengths, spots, first, count, reverb, dry.numel(), src.numel(),
+                            out=slot.pin[at:sent].numpy().view(ops.REVERB_DESC_DTYPE))
+            dev_reverb, offsets = slot.dev[at:sent], spots
         ops.prep_desc(offsets, lengths, pads, T_max, src.numel(), N, S, out=table)
         if gains is not None:             # float32 [batch] behind the descriptors: one copy carries them all
             at, sent = sent, sent + batch_size * 4
@@ -583,7 +711,10 @@ class WavDirData(Dataset):
             buf = ring['out'][k % self.OUT_DEPTH] = torch.empty(n, dtype=torch.complex64, device=device)
         out = buf[:n].view(batch_size, cnt, F)
         if speed is not None:
-            ops.speed_resample(pool, dev_speed, self.speed_table_on(device), src)
+            ops.speed_resample(pool, dev_speed, self.speed_table_on(device), dry if reverb is not None else src)
+        if reverb is not None:
+            bank = self.reverb_bank_on(device)
+            ops.reverb_apply(dry, dev_reverb, bank, bank.shape[1], src)
         ops.stft_batch(src, dev_table, T_max, window, N, S, t_begin=beg, t_count=cnt, out=out)
         if gains is not None:
             ops.mix_scale_(out, dev_gains)

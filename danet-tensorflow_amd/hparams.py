@@ -23,6 +23,8 @@ unchanged.  Differences, all deliberate:
   (the reference's `# TODO add mixing coeff ?`, `main.py:230`); every other dataset ignores them.
 * `SPEED_PERTURB_RANGE` (a fraction in [0, 0.25], default None = off) makes the `wavdir` dataset
   resample every utterance of every train batch by a drawn speed factor; every other dataset ignores it.
+* `REVERB_RT60_MAX` (seconds in [0, 1.0], default None = off) makes the `wavdir` dataset convolve every
+  utterance of every train batch with a drawn synthetic room response; every other dataset ignores it.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -79,6 +81,9 @@ DEFAULTS = {
     # speed perturbation of the `wavdir` dataset's train subset, a fraction in [0, 0.25], None = off (not in the
     # reference; include/danet_speed_hip.h)
     'SPEED_PERTURB_RANGE': None,
+    # reverberation of the `wavdir` dataset's train subset: the longest RT60 of the bank of room responses, seconds
+    # in [0, 1.0], None = off (not in the reference; include/danet_reverb_hip.h)
+    'REVERB_RT60_MAX': None,
 }
 
 
@@ -102,7 +107,7 @@ class Hyperparameter:
     '''
     Contains hyperparameter settings (reference: app/hparams.py:15-127)
     '''
-    pattern = r'[A-Z_]+'
+    pattern = r'[A-Z_][A-Z0-9_]*'      # (digits after the first letter: REVERB_RT60_MAX)
 
     def __init__(self):
         self.__dict__.update(DEFAULTS)

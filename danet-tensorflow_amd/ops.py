@@ -611,6 +611,110 @@ def speed_resample(pool, desc, table, out):
     return out
 
 
+# ---- reverberation of the wavdir dataset (include/danet_reverb_hip.h) -----------------------------------
+# On the extension library libdanet_reverb_hip.so, mapped at the first call: a wavdir run with
+# REVERB_RT60_MAX null never gets here.
+REVERB_ROWS, REVERB_MIN_TAPS, REVERB_MAX_TAPS = 32, 4, 8192     # NB (DANET_REVERB_ROWS), DANET_REVERB_MIN_TAPS / _MAX_TAPS
+REVERB_DESC_DTYPE = np.dtype([('src_offset', '<i8'), ('src_length', '<i8'), ('dst_offset', '<i8'),
+                              ('out_begin', '<i8'), ('out_count', '<i8'), ('row', '<i4'), ('reserved', '<i4')])
+
+
+def reverb_taps(R, smprate):
+    '''K = 4 * ceil(R * smprate / 4), at least REVERB_MIN_TAPS (the rule of include/danet_reverb_hip.h); one
+    above REVERB_MAX_TAPS is the caller's to refuse.  Host only, no library involved.'''
+    return max(REVERB_MIN_TAPS, 4 * int(np.ceil(float(R) * float(smprate) / 4.0)))
+
+
+def reverb_bank(R, smprate):
+    '''the float32 [NB][K] bank of room responses of REVERB_RT60_MAX = R at `smprate` (the rule of
+    include/danet_reverb_hip.h): float64 numpy, rounded once, checked to be finite.  Host only, no library
+    involved.'''
+    NB, K = REVERB_ROWS, reverb_taps(R, smprate)
+    if K > REVERB_MAX_TAPS:
+        raise ValueError('reverb_bank: REVERB_RT60_MAX = %r at SMPRATE = %r needs %d taps, more than the %d of '
+                         'include/danet_reverb_hip.h' % (R, smprate, K, REVERB_MAX_TAPS))
+    bank = np.zeros((NB, K), dtype=np.float64)
+    bank[:, 0] = 1.0
+    n = np.arange(K, dtype=np.float64)
+    for k in range(1, NB):
+        rt60 = float(R) * k / (NB - 1)
+        if rt60 <= 0:
+            continue                                                  # R = 0: no tail, the unit impulse
+        g = np.random.RandomState([1337, 2, k]).standard_normal(K)
+        t = g * np.exp(-3.0 * np.log(10.0) * n / (rt60 * float(smprate)))
+        t[0] = 0.0
+        e = float(np.sum(t * t))
+        if e > 0:
+            t *= np.sqrt(10.0 ** (-(10.0 - 10.0 * k / (NB - 1)) / 10.0) / e)
+        e = float(np.sum(t * t))
+        t[0] = 1.0
+        bank[k] = t / np.sqrt(1.0 + e)
+    bank = bank.astype(np.float32)
+    if not np.isfinite(bank).all():
+        raise ValueError('reverb_bank: the bank of REVERB_RT60_MAX = %r is not finite' % (R,))
+    return bank
+
+
+def reverb_desc(src_offsets, src_lengths, dst_offsets, out_begin, out_count, rows, src_len, dst_len, out=None):
+    '''the validated descriptor table of one launch as a numpy record array (REVERB_DESC_DTYPE; into `out`
+    when given).  Everything the kernel would have to clamp is a ValueError HERE, before any upload or
+    launch: a source span outside the pool, a span outside [0, length), a written span outside the buffer or
+    across another, a row outside [0, REVERB_ROWS).'''
+    n = len(src_offsets)
+    d = np.zeros(n, REVERB_DESC_DTYPE) if out is None else out
+    assert d.dtype == REVERB_DESC_DTYPE and d.shape == (n,)
+    d['src_offset'], d['src_length'], d['dst_offset'] = src_offsets, src_lengths, dst_offsets
+    d['out_begin'], d['out_count'], d['row'], d['reserved'] = out_begin, out_count, rows, 0
+    so, sl, do, ob, oc, rw = (d[k].astype(np.int64) for k in ('src_offset', 'src_length', 'dst_offset', 'out_begin',
+                                                              'out_count', 'row'))
+    bad = np.nonzero((so < 0) | (sl < 1) | (so + sl > src_len))[0]
+    if len(bad):
+        u = int(bad[0])
+        raise ValueError('reverb_apply: utterance %d [%d, %d) is outside the pool of %d samples'
+                         % (u, so[u], so[u] + sl[u], src_len))
+    bad = np.nonzero((rw < 0) | (rw >= REVERB_ROWS))[0]
+    if len(bad):
+        raise ValueError('reverb_apply: utterance %d: row = %d is outside [0, %d)' % (bad[0], rw[bad[0]], REVERB_ROWS))
+    bad = np.nonzero((ob < 0) | (oc < 0) | (ob + oc > sl))[0]
+    if len(bad):
+        u = int(bad[0])
+        raise ValueError('reverb_apply: utterance %d: the span [%d, %d) is outside its %d samples'
+                         % (u, ob[u], ob[u] + oc[u], sl[u]))
+    lo, hi = do + ob, do + ob + oc
+    order = np.argsort(lo, kind='stable')
+    if np.any(lo < 0) or np.any(hi > dst_len) or np.any(lo[order][1:] < hi[order][:-1]):
+        raise ValueError('reverb_apply: the written spans must lie inside the buffer of %d samples and '
+                         'apart from each other' % dst_len)
+    return d
+
+
+def reverb_apply(src, desc, bank, n_taps, out):
+    '''every utterance `desc` describes convolved with its row of `bank` from the float32 device vector `src`
+    into the float32 device vector `out`, ONE launch (danet_reverb_apply); nothing of `out` outside the asked
+    spans is touched.  desc: the table of ops.reverb_desc -- a numpy record array (validated again and uploaded
+    here) or a device uint8 / int64 tensor of 48-byte rows the caller has validated and uploaded.
+    bank: ops.reverb_bank(R, smprate) on the device, float32 [32, n_taps].  There is no CPU fallback.'''
+    for t in (src, out):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()
+    assert bank.is_cuda and bank.dtype == torch.float32 and bank.is_contiguous()
+    assert tuple(bank.shape) == (REVERB_ROWS, n_taps) and bank.device == src.device == out.device
+    assert src.data_ptr() != out.data_ptr()
+    if not torch.is_tensor(desc):
+        desc = np.asarray(desc)
+        if desc.dtype != REVERB_DESC_DTYPE:
+            raise TypeError('reverb_apply: desc must be a REVERB_DESC_DTYPE record array or a device tensor')
+        reverb_desc(desc['src_offset'], desc['src_length'], desc['dst_offset'], desc['out_begin'], desc['out_count'],
+                    desc['row'], src.numel(), out.numel())
+        desc = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8).copy()).to(src.device)
+    row = REVERB_DESC_DTYPE.itemsize
+    assert desc.is_cuda and desc.is_contiguous() and (desc.numel() * desc.element_size()) % row == 0
+    n_utt = desc.numel() * desc.element_size() // row
+    with _lib.timed('reverb_apply'):
+        _lib.reverb_check(_lib.load_reverb().danet_reverb_apply(
+            _lib.stream(), n_utt, ptr(src), src.numel(), ptr(desc), ptr(bank), int(n_taps), ptr(out), out.numel()))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # LSTM layer (both directions), raw forward / backward on time-major tensors
 # ---------------------------------------------------------------------------
