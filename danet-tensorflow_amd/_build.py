@@ -1,5 +1,5 @@
 '''
-Builds the seven HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the eight HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -11,6 +11,7 @@ Builds the seven HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_mix_hip.so           csrc/mix/*.hip           include/danet_mix_hip.h
     libdanet_speed_hip.so         csrc/speed/*.hip         include/danet_speed_hip.h
     libdanet_reverb_hip.so        csrc/reverb/*.hip        include/danet_reverb_hip.h
+    libdanet_metric_hip.so        csrc/metric/*.hip        include/danet_metric_hip.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -59,6 +60,11 @@ LIB, CONV_LIB, DROPOUT_LIB, PREP_LIB, MIX_LIB, SPEED_LIB = (spec.out for spec in
 REVERB = _extension('reverb')
 LATER_LIBRARIES = (REVERB,)
 REVERB_LIB = REVERB.out
+# build() stays the seven libraries above.  Every library after them goes HERE, appended: build_all() runs
+# build() and then over EXTENSIONS, and nothing pins the length of this tuple
+METRIC = _extension('metric')
+EXTENSIONS = (METRIC,)
+METRIC_LIB = METRIC.out
 
 
 def _sources(src_dir):
@@ -96,7 +102,7 @@ def _link(objs, out, src_dir):
         raise RuntimeError('link failed:\n%s\n%s' % (r.stdout, r.stderr))
 
 
-def _build_library(spec, force, verbose):
+def _build_spec(spec, force, verbose):
     hdr_m = max((os.path.getmtime(h) for pattern in spec.headers for h in glob.glob(pattern)), default=0.0)
     res = _compile_all(spec.src_dir, os.path.join(spec.src_dir, 'build'), force, hdr_m)
     objs = [o for o, _ in res]
@@ -109,10 +115,23 @@ def _build_library(spec, force, verbose):
     return spec.out
 
 
+def _build_library(spec, force, verbose):
+    return _build_spec(spec, force, verbose)
+
+
 def build(force=False, verbose=True):
+    '''the seven libraries of LIBRARIES + LATER_LIBRARIES (build_all: every library)'''
     for spec in LIBRARIES + LATER_LIBRARIES:
         _build_library(spec, force, verbose)
     return LIB
+
+
+def build_all(force=False, verbose=True):
+    '''build(), then every record of EXTENSIONS -> [every shared object built, in order]'''
+    build(force, verbose)
+    for spec in EXTENSIONS:
+        _build_spec(spec, force, verbose)
+    return [spec.out for spec in LIBRARIES + LATER_LIBRARIES + EXTENSIONS]
 
 
 def build_conv(force=False, verbose=True):
@@ -139,6 +158,10 @@ def build_reverb(force=False, verbose=True):
     return _build_library(REVERB, force, verbose)
 
 
+def build_metric(force=False, verbose=True):
+    return _build_spec(METRIC, force, verbose)
+
+
 def build_variant(name, defs):
     '''A/B variant csrc/libdanet_hip_<name>.so compiled with extra -D switches (e.g.
     name='accmath', defs=['-DDANET_LSTM_ACCURATE_MATH']; name='trace',
@@ -162,4 +185,4 @@ if __name__ == '__main__':
         i = sys.argv.index('--variant')
         print(build_variant(sys.argv[i + 1], sys.argv[i + 2:]))
     else:
-        build(force='--force' in sys.argv)
+        build_all(force='--force' in sys.argv)

@@ -1,7 +1,7 @@
 '''
-ctypes binding of the seven HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
-libdanet_hip.so and the conv, dropout, prep, mix, speed and reverb extension libraries.  Each is described once,
-by a record of ALL_LIBRARIES or LATER_LIBRARIES; one loader (_load) and one error check (_check) serve them all.
+ctypes binding of the eight HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb and metric extension libraries.  Each is described
+once, by a record of ALL_LIBRARIES, LATER_LIBRARIES or EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
 RuntimeError is raised.  PyTorch is used only to own device memory and streams;
@@ -178,14 +178,25 @@ REVERB_PROTOTYPES = {
     'danet_reverb_apply': (c_int, [c_p, c_int, c_p, c_i64, c_p, c_p, c_int, c_p, c_i64]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_metric_hip.h
+METRIC_PROTOTYPES = {
+    'danet_metric_abi_version': (c_int, []),
+    'danet_metric_last_error': (ctypes.c_char_p, []),
+    'danet_metric_workspace_bytes': (c_sz, [c_int, c_int, c_int, c_int, c_int]),
+    'danet_metric_synth': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
+    'danet_metric_gram': (c_int, [c_p, c_int, c_int, c_i64, c_p, c_p]),
+    'danet_metric_si_sdr': (c_int, [c_p, c_int, c_int, c_p, c_p, c_p, c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Seven shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Eight shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
 # records the per-record tests are written against, by position, ALL_LIBRARIES those and SPEED, and
-# _build.LIBRARIES the same six; every library after them is APPENDED to LATER_LIBRARIES, here and in
-# _build.py, and is served by the same Library record type, _load, _check and _build_library.
+# _build.LIBRARIES the same six, LATER_LIBRARIES the seventh; every library after them is APPENDED to EXTENSIONS,
+# here and in _build.py (which builds them in build_all), and is served by the same Library record type, _load
+# and _check.
 #   name: '' for the core; so: the file under csrc/; path_var / handle_var: the module globals that hold
 #   its path (read when it is loaded: tests and tools assign to it) and its CDLL (None until then);
 #   prefix: danet_<p>abi_version and danet_<p>last_error follow from it; needs: who needs it, for the
@@ -220,6 +231,15 @@ REVERB = Library('reverb', 'libdanet_reverb_hip.so', 'REVERB_LIB_PATH', '_reverb
 LIBRARIES = (CORE, CONV, DROPOUT, PREP, MIX)
 ALL_LIBRARIES = LIBRARIES + (SPEED,)
 LATER_LIBRARIES = (REVERB,)
+# The three tuples above are closed (tests pin them by length and content).  EXTENSIONS is the OPEN tuple: every
+# library from the eighth on is appended to it, here and in _build.py, and nothing pins its length -- a test of a
+# new library asserts `ITS_RECORD in EXTENSIONS`, never what else is there.
+# loaded at the first valid / test step with EVAL_SI_SDR true only (ops.si_sdr): a run with the key null never
+# maps it
+METRIC_ABI_VERSION = 1
+METRIC = Library('metric', 'libdanet_metric_hip.so', 'METRIC_LIB_PATH', '_metric', METRIC_PROTOTYPES,
+                 METRIC_ABI_VERSION, 'danet_metric_', 'EVAL_SI_SDR needs the HIP extension library')
+EXTENSIONS = (METRIC,)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -229,7 +249,8 @@ PREP_LIB_PATH = os.path.join(_CSRC, PREP.so)
 MIX_LIB_PATH = os.path.join(_CSRC, MIX.so)
 SPEED_LIB_PATH = os.path.join(_CSRC, SPEED.so)
 REVERB_LIB_PATH = os.path.join(_CSRC, REVERB.so)
-_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = None
+METRIC_LIB_PATH = os.path.join(_CSRC, METRIC.so)
+_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = None
 _lock = threading.Lock()
 
 
@@ -349,6 +370,17 @@ def load_reverb():
 def reverb_check(rc):
     if rc != 0:
         _check(REVERB, rc)
+
+
+def load_metric():
+    if _metric is not None:
+        return _metric
+    return _load(METRIC)
+
+
+def metric_check(rc):
+    if rc != 0:
+        _check(METRIC, rc)
 
 
 # ---- switches ------------------------------------------------------------------

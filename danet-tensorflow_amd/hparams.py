@@ -25,6 +25,8 @@ unchanged.  Differences, all deliberate:
   resample every utterance of every train batch by a drawn speed factor; every other dataset ignores it.
 * `REVERB_RT60_MAX` (seconds in [0, 1.0], default None = off) makes the `wavdir` dataset convolve every
   utterance of every train batch with a drawn synthetic room response; every other dataset ignores it.
+* `EVAL_SI_SDR` (true / false, default None = off) makes `Model.valid_step` return `SI-SDR` and `SI-SDRi` of the
+  separated waveforms next to `loss` and `SNR`, for every dataset; `train_step` and `infer` never compute it.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -84,6 +86,9 @@ DEFAULTS = {
     # reverberation of the `wavdir` dataset's train subset: the longest RT60 of the bank of room responses, seconds
     # in [0, 1.0], None = off (not in the reference; include/danet_reverb_hip.h)
     'REVERB_RT60_MAX': None,
+    # `valid` / `test` also report the SI-SDR of the separated waveforms and its improvement over the mixture, dB:
+    # true = on, null / false = off (not in the reference; include/danet_metric_hip.h)
+    'EVAL_SI_SDR': None,
 }
 
 

@@ -108,6 +108,7 @@ class Model(object):
     def build(self):
         '''create sub-modules (main.py:210-211, 249-250, 263-270), materialise
         variables with one dry forward, then flatten them for the optimiser.'''
+        self.eval_si_sdr = self._check_eval_si_sdr()
         self.encoder = hparams.get_encoder()(self, 'encoder')
         self.estimator = hparams.get_estimator(
             hparams.TRAIN_ESTIMATOR_METHOD)(self, 'train_estimator')
@@ -132,6 +133,30 @@ class Model(object):
         dist.broadcast_params_(self._flat)
         ops.weights_written(self._flat)
         return self
+
+    @staticmethod
+    def _check_eval_si_sdr():
+        '''EVAL_SI_SDR (null / false: off) -> bool; ValueError naming the key that rules the metric out'''
+        v = getattr(hparams, 'EVAL_SI_SDR', None)
+        if v is not None and not isinstance(v, bool):
+            raise ValueError('EVAL_SI_SDR must be null, true or false (got %r)' % (v,))
+        if not v:
+            return False
+        N, S = hparams.FFT_SIZE, hparams.FFT_STRIDE
+        if N < 64 or N > 1024 or N & (N - 1):
+            raise ValueError('EVAL_SI_SDR needs FFT_SIZE to be a power of two in 64..1024 (got FFT_SIZE = %d): the '
+                             'envelope of danet_metric_synth' % N)
+        if 2 * S > N:
+            raise ValueError('EVAL_SI_SDR needs FFT_STRIDE <= FFT_SIZE / 2 (got FFT_STRIDE = %d at FFT_SIZE = %d): '
+                             'beyond half a window the overlap-added squared window can reach 0 at the window '
+                             'edges' % (S, N))
+        if 8 * S < N:
+            raise ValueError('EVAL_SI_SDR needs FFT_STRIDE >= FFT_SIZE / 8 (got FFT_STRIDE = %d at FFT_SIZE = %d): '
+                             'the frames that overlap one tile of hops must fit in the 64 KiB of LDS the synthesis '
+                             'kernel uses' % (S, N))
+        if hparams.MAX_N_SIGNAL > ops.METRIC_MAX_C:
+            raise ValueError('EVAL_SI_SDR needs MAX_N_SIGNAL <= %d (got %d)' % (ops.METRIC_MAX_C, hparams.MAX_N_SIGNAL))
+        return True
 
     def _flatten(self):
         n = sum(self.vars[k].numel() for k in self._order)
@@ -422,8 +447,13 @@ class Model(object):
         ops.poll_status(self.device)
         with torch.no_grad():
             out = self.forward(s_src_signals, with_valid=True, with_train=False)
+            res = dict(loss=out['valid_loss'], SNR=out['valid_SNR'])
+            if self.eval_si_sdr:
+                # the waveform metric does its own permutation search: the estimates go in unpermuted
+                est = ops.reattach_phase(out['sep_pwr_valid'], out['phasor'])
+                res['SI-SDR'], res['SI-SDRi'] = ops.si_sdr(s_src_signals, est)[:2]
         ops.step_done(self.device, collective_consistent=not dist.is_dist())
-        return dict(loss=out['valid_loss'], SNR=out['valid_SNR'])
+        return res
 
     def infer(self, s_mixed_signals):
         '''`g_sess.run(infer_fetches, {s_mixed_signals: ...})` (main.py:384-385,

@@ -715,6 +715,121 @@ def reverb_apply(src, desc, bank, n_taps, out):
     return out
 
 
+# ---- waveform metric of valid / test (include/danet_metric_hip.h) -------------------------------------
+# On the extension library libdanet_metric_hip.so, mapped at the first call: a run with EVAL_SI_SDR null never
+# gets here.  Three launches: spectra -> waveforms -> Gram matrices -> decibels.
+METRIC_MAX_C = 4                                     # DANET_METRIC_MAX_C
+_metric_ws = {}          # (device index, stream, B, C, T, N, S) -> (scratch, wav, G, per_utt, mean2, perm_idx)
+_metric_windows = {}     # (device index, window bytes) -> float32 device vector
+
+
+def _metric_window(dev):
+    '''hparams.FFT_WND as a float32 device vector, uploaded once per (device, window)'''
+    from .hparams import hparams
+    w = np.ascontiguousarray(np.asarray(hparams.FFT_WND, dtype=np.float32))
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), w.tobytes())
+    t = _metric_windows.get(key)
+    if t is None:
+        t = _metric_windows[key] = torch.from_numpy(w.copy()).to(dev)
+    return t
+
+
+def _metric_workspace(B, C, T, N, S, dev):
+    '''(buffer, wav, G, per_utt, mean2, perm_idx): the views one shape cuts out of the grow-only scratch of this
+    (device, stream), in the layout of danet_metric_workspace_bytes; cached per shape'''
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
+           torch.cuda.current_stream().cuda_stream, B, C, T, N, S)
+    hit = _metric_ws.get(key)
+    if hit is not None and _lib._ws.get(key[:2] + ('metric',)) is hit[0]:
+        return hit
+    nbytes = _lib.load_metric().danet_metric_workspace_bytes(B, C, T, N, S)
+    if nbytes == ctypes.c_size_t(-1).value:
+        _lib.metric_check(-1)
+    buf = _lib.workspace(nbytes, dev, 'metric')
+    M, Ls = 2 * C, (T - 1) * S
+    views, off = [], 0
+    for shape, dtype, size in (((B, M, Ls), torch.float32, 4), ((B, M, M), torch.float64, 8),
+                               ((B, 2), torch.float64, 8), ((2,), torch.float64, 8), ((B,), torch.int32, 4)):
+        n = int(np.prod(shape)) * size
+        views.append(buf[off:off + n].view(dtype).view(shape))
+        off += (n + 255) & ~255
+    assert off == nbytes, (off, nbytes)
+    if len(_metric_ws) >= 64:
+        _metric_ws.clear()
+    hit = _metric_ws[key] = (buf,) + tuple(views)
+    return hit
+
+
+def metric_synth(src, est, fft_stride, window=None, out=None):
+    '''references and UNPERMUTED estimates, complex64 [B, C, T, F] -> float32 waveforms [B, 2C, (T - 1) * S],
+    references first, ONE launch (danet_metric_synth: overlap-add with an exact window-sum division).
+    window: float32 device vector [N] (default hparams.FFT_WND, uploaded once).'''
+    assert src.is_cuda and src.dtype == torch.complex64 and src.dim() == 4, (src.dtype, src.shape)
+    assert est.is_cuda and est.dtype == torch.complex64 and est.shape == src.shape and est.device == src.device
+    src, est = src.contiguous(), est.contiguous()
+    B, C, T, F = src.shape
+    N = 2 * (F - 1)
+    window = _metric_window(src.device) if window is None else _f32(window).contiguous()
+    assert window.numel() == N and window.device == src.device, (window.numel(), N)
+    if out is None:
+        out = torch.empty(B, 2 * C, max(T - 1, 0) * fft_stride, dtype=torch.float32, device=src.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, 2 * C, (T - 1) * fft_stride)
+    with _lib.timed('metric_synth'):
+        _lib.metric_check(_lib.load_metric().danet_metric_synth(
+            _lib.stream(), B, C, T, N, fft_stride, ptr(torch.view_as_real(src)), ptr(torch.view_as_real(est)),
+            ptr(window), ptr(out)))
+    return out
+
+
+def metric_gram(wav, out=None):
+    '''float32 [B, M, Ls] -> float64 Gram matrices [B, M, M], ONE launch (danet_metric_gram: float64 products
+    and sums over a fixed tree; symmetric bit for bit)'''
+    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.is_contiguous()
+    B, M, Ls = wav.shape
+    if out is None:
+        out = torch.empty(B, M, M, dtype=torch.float64, device=wav.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B, M, M)
+    with _lib.timed('metric_gram'):
+        _lib.metric_check(_lib.load_metric().danet_metric_gram(_lib.stream(), B, M, Ls, ptr(wav), ptr(out)))
+    return out
+
+
+def metric_finalize(G, out=None):
+    '''float64 Gram matrices [B, 2C, 2C] -> (mean2 [2], per_utt [B, 2], perm_idx int32 [B]), ONE launch
+    (danet_metric_si_sdr); out: optional (per_utt, perm_idx, mean2) to write into'''
+    assert G.is_cuda and G.dtype == torch.float64 and G.dim() == 3 and G.is_contiguous() and G.shape[1] == G.shape[2]
+    B, M = G.shape[0], G.shape[1]
+    assert M % 2 == 0, M
+    if out is None:
+        out = (torch.empty(B, 2, dtype=torch.float64, device=G.device),
+               torch.empty(B, dtype=torch.int32, device=G.device), torch.empty(2, dtype=torch.float64, device=G.device))
+    per_utt, perm_idx, mean2 = out
+    with _lib.timed('metric_si_sdr'):
+        _lib.metric_check(_lib.load_metric().danet_metric_si_sdr(_lib.stream(), B, M // 2, ptr(G), ptr(per_utt),
+                                                                 ptr(perm_idx), ptr(mean2)))
+    return mean2, per_utt, perm_idx
+
+
+def si_sdr(src, est, fft_stride=None):
+    '''SI-SDR and SI-SDRi (dB) of the waveforms of the UNPERMUTED estimates `est` against the references
+    `src`, both complex64 [B, C, T, F] -> (si_sdr, si_sdri, per_utt [B, 2], perm_idx [B]): float64 / int32 device
+    tensors of the caller's own (allocated here, written by the finalize kernel; the waveforms and Gram
+    matrices live in a scratch cached per shape).  Three launches and nothing else on the device, no host
+    synchronisation.'''
+    from .hparams import hparams
+    S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
+    B, C, T, F = src.shape
+    dev = src.device
+    ws = _metric_workspace(B, C, T, 2 * (F - 1), S, dev)
+    wav, G = ws[1], ws[2]
+    metric_synth(src, est, S, out=wav)
+    metric_gram(wav, out=G)
+    mean2, per_utt, perm_idx = metric_finalize(G, out=(torch.empty(B, 2, dtype=torch.float64, device=dev),
+                                                       torch.empty(B, dtype=torch.int32, device=dev),
+                                                       torch.empty(2, dtype=torch.float64, device=dev)))
+    return mean2[0], mean2[1], per_utt, perm_idx
+
+
 # ---------------------------------------------------------------------------
 # LSTM layer (both directions), raw forward / backward on time-major tensors
 # ---------------------------------------------------------------------------
