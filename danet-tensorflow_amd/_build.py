@@ -1,5 +1,5 @@
 '''
-Builds the eight HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the nine HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -12,6 +12,7 @@ Builds the eight HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_speed_hip.so         csrc/speed/*.hip         include/danet_speed_hip.h
     libdanet_reverb_hip.so        csrc/reverb/*.hip        include/danet_reverb_hip.h
     libdanet_metric_hip.so        csrc/metric/*.hip        include/danet_metric_hip.h
+    libdanet_noise_hip.so         csrc/noise/*.hip         include/danet_noise_hip.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -63,8 +64,10 @@ REVERB_LIB = REVERB.out
 # build() stays the seven libraries above.  Every library after them goes HERE, appended: build_all() runs
 # build() and then over EXTENSIONS, and nothing pins the length of this tuple
 METRIC = _extension('metric')
-EXTENSIONS = (METRIC,)
+NOISE = _extension('noise')
+EXTENSIONS = (METRIC, NOISE)
 METRIC_LIB = METRIC.out
+NOISE_LIB = NOISE.out
 
 
 def _sources(src_dir):
@@ -160,6 +163,10 @@ def build_reverb(force=False, verbose=True):
 
 def build_metric(force=False, verbose=True):
     return _build_spec(METRIC, force, verbose)
+
+
+def build_noise(force=False, verbose=True):
+    return _build_spec(NOISE, force, verbose)
 
 
 def build_variant(name, defs):

@@ -1,6 +1,6 @@
 '''
-ctypes binding of the eight HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
-libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb and metric extension libraries.  Each is described
+ctypes binding of the nine HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric and noise extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES or EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -188,8 +188,15 @@ METRIC_PROTOTYPES = {
     'danet_metric_si_sdr': (c_int, [c_p, c_int, c_int, c_p, c_p, c_p, c_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_noise_hip.h
+NOISE_PROTOTYPES = {
+    'danet_noise_abi_version': (c_int, []),
+    'danet_noise_last_error': (ctypes.c_char_p, []),
+    'danet_noise_frontend_fwd': (c_int, [c_p, c_int, c_int, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Eight shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Nine shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -239,7 +246,12 @@ LATER_LIBRARIES = (REVERB,)
 METRIC_ABI_VERSION = 1
 METRIC = Library('metric', 'libdanet_metric_hip.so', 'METRIC_LIB_PATH', '_metric', METRIC_PROTOTYPES,
                  METRIC_ABI_VERSION, 'danet_metric_', 'EVAL_SI_SDR needs the HIP extension library')
-EXTENSIONS = (METRIC,)
+# loaded at the first wavdir TRAIN step with NOISE_DIR set only (ops.noise_frontend): a run with the key null, and
+# every evaluation sweep, never maps it
+NOISE_ABI_VERSION = 1
+NOISE = Library('noise', 'libdanet_noise_hip.so', 'NOISE_LIB_PATH', '_noise', NOISE_PROTOTYPES,
+                NOISE_ABI_VERSION, 'danet_noise_', 'NOISE_DIR needs the HIP extension library')
+EXTENSIONS = (METRIC, NOISE)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -250,7 +262,8 @@ MIX_LIB_PATH = os.path.join(_CSRC, MIX.so)
 SPEED_LIB_PATH = os.path.join(_CSRC, SPEED.so)
 REVERB_LIB_PATH = os.path.join(_CSRC, REVERB.so)
 METRIC_LIB_PATH = os.path.join(_CSRC, METRIC.so)
-_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = None
+NOISE_LIB_PATH = os.path.join(_CSRC, NOISE.so)
+_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = None
 _lock = threading.Lock()
 
 
@@ -381,6 +394,17 @@ def load_metric():
 def metric_check(rc):
     if rc != 0:
         _check(METRIC, rc)
+
+
+def load_noise():
+    if _noise is not None:
+        return _noise
+    return _load(NOISE)
+
+
+def noise_check(rc):
+    if rc != 0:
+        _check(NOISE, rc)
 
 
 # ---- switches ------------------------------------------------------------------

@@ -45,7 +45,8 @@ def train_epoch(model, batches, out=sys.stdout, sync_feed=None):
     cropped and uploaded one step ahead (feed.BatchFeed), the per-step metrics stay on the device
     until the epoch mean is read (feed.StepReport).  `batches` may also be a feed.EpochSource: a dataset
     that builds its batches on the device (wavdir) is then asked for them directly (feed.open_feed)
-    instead of going through BatchFeed.  sync_feed=True is the reference's literal
+    instead of going through BatchFeed.  A feed.NoisyBatch (src, noise, gain) is unpacked into train_step's three
+    arguments.  sync_feed=True is the reference's literal
     form -- blocking upload, `float()` of every metric every step -- kept for the equality test
     and `bench.py --e2e --sync-feed`.  Returns (OrderedDict of epoch means, number of batches).
     LIFETIME of a batch tensor in the 'ahead' mode: it is a view of one of three reused device
@@ -57,7 +58,10 @@ def train_epoch(model, batches, out=sys.stdout, sync_feed=None):
     src = feed.open_feed(batches, model.device, hparams.MAX_TRAIN_LEN, sync_feed)
     report = feed.StepReport(flush_every=1 if sync_feed else 1024)
     for spectra in src:
-        step_fetch = model.train_step(spectra)
+        if isinstance(spectra, feed.NoisyBatch):      # the wavdir dataset with NOISE_DIR set
+            step_fetch = model.train_step(spectra.src, s_noise=spectra.noise, s_noise_gain=spectra.gain)
+        else:
+            step_fetch = model.train_step(spectra)
         model.reset_state()
         out.write(':')
         out.flush()

@@ -8,8 +8,12 @@ STFT kernel (include/danet_prep_hip.h), -- with MIX_SNR_RANGE / MIX_LEVEL_RANGE 
 applies the drawn per-utterance gains (include/danet_mix_hip.h), -- with SPEED_PERTURB_RANGE set -- one
 launch in front of the STFT that resamples every train utterance by its drawn speed (include/danet_speed_hip.h)
 and -- with REVERB_RT60_MAX set -- one launch behind that one that convolves every train utterance with its drawn
-room response (include/danet_reverb_hip.h).
+room response (include/danet_reverb_hip.h).  With NOISE_DIR set every train batch carries one more STFT launch over
+a pool of noise recordings, and the model's front-end adds that noise to the mixture at a drawn SNR while the
+targets stay clean (include/danet_noise_hip.h).
 '''
+import collections
+import math
 import os
 import random
 from math import ceil
@@ -25,7 +29,9 @@ class Dataset(object):
         self.is_loaded = False
 
     def epoch(self, subset, batch_size, shuffle=False):
-        '''yields (numpy batch [batch_size, T, F],) per batch.  Two OPTIONAL, independent extensions, both
+        '''yields (numpy batch [batch_size, T, F],) per batch -- or (that, noise [batch_size / MAX_N_SIGNAL, T, F]):
+        a second element is a component of every mixture that is not a target (feed.BatchFeed carries it through as
+        a feed.NoisyBatch; only wavdir with NOISE_DIR set yields one).  Two OPTIONAL, independent extensions, both
         looked up by cli through feed.EpochSource: an epoch() that computes its batches on a GPU may take a
         further keyword `device=None` (it is then handed the model's device); a dataset that can build
         the cropped batch on the device offers
@@ -145,6 +151,11 @@ class _DescSlot(object):
     __slots__ = ('pin', 'dev', 'event', 'used')
 
 
+# the noise of one train batch (WavDirData.plan_noise): per mixture the row into the noise pool (offsets, lengths,
+# pads: a danet_prep_utt_t row), the float32 gain, the float64 it was rounded from, the file and the SNR drawn
+NoisePlan = collections.namedtuple('NoisePlan', 'offsets lengths pads gains gains64 files snr')
+
+
 @hparams.register_dataset('wavdir')
 class WavDirData(Dataset):
     '''a folder of single-channel WAV files: hparams.DATASET_DIR/{train,valid,test}/**/*.wav, taken in
@@ -195,7 +206,24 @@ class WavDirData(Dataset):
     whole utterances, epoch_device() only for the samples the cropped frames read (reverb_span); the kernel's
     values do not depend on the span, so both routes give the same batches bit for bit.  The 48-byte reverb
     descriptors ride in the pinned ring behind the speed descriptors and before the gains.  With MIX_SNR_RANGE
-    the powers stay those of the stored files.'''
+    the powers stay those of the stored files.
+
+    ADDITIVE NOISE (hparams.NOISE_DIR = a folder of noise recordings, NOISE_SNR_MIN = lo, NOISE_SNR_MAX = hi, dB,
+    -30 <= lo <= hi <= 60; all three default None = off: no launch, no allocation, no draw, libdanet_noise_hip.so not
+    mapped).  `train` only; `valid` / `test` batches are those without the keys, bit for bit (EVAL_SI_SDR derives its
+    mixture baseline from the clean references by linearity).  NOISE_DIR/**/*.wav is discovered and decoded like the
+    dataset's own files into ONE more pool (files shorter than FFT_SIZE skipped and counted).  After a train batch
+    is planned as without the keys, plan_noise (the rule include/danet_noise_hip.h writes out) draws per MIXTURE a
+    noise file, a position and an SNR from a fifth RandomState, seeded by (dist.shard_seed(1337), subset index, 3):
+    a segment of (T_max - 1) * FFT_STRIDE samples of a long file, or a short file whole, placed like a short
+    utterance; the gain sets the drawn SNR against the sum of the sources' stored whole-file powers times their
+    squared mix gains (so libdanet_mix_hip.so is mapped for its two power launches even with the MIX_* keys null).
+    The noise is NOT a row of the batch: ONE more ops.stft_batch launch over the noise pool writes it into a ring of
+    OUT_DEPTH buffers of its own, epoch_device() yields feed.NoisyBatch(src, noise, gains), and Model.train_step
+    hands the three to ops.noise_frontend in place of ops.frontend -- the targets stay the clean sources.  The
+    24-byte noise descriptors and the gains ride in the pinned ring behind the mix gains.  epoch() yields
+    (spectra, noise) with the noise already scaled (ops.mix_scale_: the same single rounding), so both routes give
+    the same mixture bit for bit.'''
     SUBSETS = ('train', 'valid', 'test')
     DESC_DEPTH = 8        # pinned descriptor tables in flight
     OUT_DEPTH = 3         # output buffers: a yielded batch stays valid while the next two are drawn
@@ -212,6 +240,10 @@ class WavDirData(Dataset):
         self._speed_rng, self._speed_table, self._speed_scratch = {}, {}, {}
         self.reverb_rt60 = None     # read from hparams by load_host
         self._reverb_rng, self._reverb_bank, self._reverb_scratch = {}, {}, {}
+        self.noise_dir = self.noise_snr = None      # read from hparams by load_host: folder, (lo, hi)
+        self.noise_files, self.noise_lengths, self.noise_offsets = [], None, None
+        self.noise_pool_host, self.noise_skipped, self.noise_power = None, 0, None
+        self._noise_rng, self._noise_pool_dev = {}, {}
         self._alias = False
 
     # ---- host half -------------------------------------------------------------------------------
@@ -283,11 +315,74 @@ class WavDirData(Dataset):
                                                                                   ops.REVERB_MAX_TAPS))
         return v
 
+    NOISE_SNR_LIMITS = (-30.0, 60.0)
+
+    @staticmethod
+    def noise_keys():
+        '''(NOISE_DIR, (NOISE_SNR_MIN, NOISE_SNR_MAX)) or (None, None) with all three null; anything else is a
+        ValueError that names the offending key: a folder that is not a string, a folder without both bounds (the
+        missing bound is named), a bound without the folder (NOISE_DIR is named), a bound that is a bool, not a
+        number, outside [-30, 60] dB, or lo > hi'''
+        folder = getattr(hparams, 'NOISE_DIR', None)
+        keys = ('NOISE_SNR_MIN', 'NOISE_SNR_MAX')
+        raw = [getattr(hparams, k, None) for k in keys]
+        if folder is not None and not isinstance(folder, str):
+            raise ValueError('hparams.NOISE_DIR must be null or the path of a folder of noise recordings, got %r'
+                             % (folder,))
+        lo_lim, hi_lim = WavDirData.NOISE_SNR_LIMITS
+        vals = []
+        for key, v in zip(keys, raw):
+            if v is not None:
+                if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo_lim <= v <= hi_lim:
+                    raise ValueError('hparams.%s must be null or a number of dB in [%g, %g], got %r'
+                                     % (key, lo_lim, hi_lim, v))
+                v = float(v)
+            vals.append(v)
+        if folder is None:
+            for key, v in zip(keys, vals):
+                if v is not None:
+                    raise ValueError('hparams.%s is set but hparams.NOISE_DIR is null: additive noise needs NOISE_DIR, '
+                                     'NOISE_SNR_MIN and NOISE_SNR_MAX together' % key)
+            return None, None
+        for key, v in zip(keys, vals):
+            if v is None:
+                raise ValueError('hparams.NOISE_DIR is set but hparams.%s is null: additive noise needs NOISE_DIR, '
+                                 'NOISE_SNR_MIN and NOISE_SNR_MAX together' % key)
+        if vals[0] > vals[1]:
+            raise ValueError('hparams.NOISE_SNR_MIN = %r is above hparams.NOISE_SNR_MAX = %r' % (vals[0], vals[1]))
+        return folder, (vals[0], vals[1])
+
+    @property
+    def noise_on(self):
+        return self.noise_dir is not None
+
+    def load_noise_host(self, out=None):
+        '''discover, decode and resample NOISE_DIR into ONE host pool, exactly like a subset's own files'''
+        folder = self.noise_dir
+        if not os.path.isdir(folder):
+            raise IOError('wavdir: NOISE_DIR folder %s not found' % folder)
+        files, waves, skipped = [], [], 0
+        for fn in self.discover(folder):
+            w = self.read_wave(fn)
+            if len(w) < hparams.FFT_SIZE:
+                skipped += 1
+                continue
+            files.append(fn)
+            waves.append(w)
+        print('wavdir noise: %d files, %d shorter than FFT_SIZE skipped' % (len(files), skipped), file=out)
+        if not files:
+            raise IOError('wavdir: no usable WAV file under NOISE_DIR = %s' % folder)
+        lens = np.asarray([len(w) for w in waves], dtype=np.int64)
+        self.noise_files, self.noise_lengths, self.noise_skipped = files, lens, skipped
+        self.noise_offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        self.noise_pool_host = np.concatenate(waves)
+
     def load_host(self, out=None):
         '''discover, decode and resample every subset into host pools (no device involved)'''
         self.mix_snr_range, self.mix_level_range = self.mix_ranges()
         self.speed_range = self.speed_perturb_range()
         self.reverb_rt60 = self.reverb_rt60_max()
+        self.noise_dir, self.noise_snr = self.noise_keys()
         root = hparams.DATASET_DIR
         if root is None:
             raise ValueError('the wavdir dataset needs hparams.DATASET_DIR: the folder that holds '
@@ -320,6 +415,8 @@ class WavDirData(Dataset):
         if self._alias:                   # app/datasets/timit.py:111-113
             for table in (self.files, self.lengths, self.offsets, self.frames, self.pool_host, self.skipped):
                 table['valid'] = table['test']
+        if self.noise_on:
+            self.load_noise_host(out)
 
     def install_and_load(self):
         self.load_host()
@@ -434,6 +531,51 @@ class WavDirData(Dataset):
                     first[u], count[u] = lo, hi - lo
         return first, count
 
+    # ---- additive noise: the draw, the segment and the gain (host, no device; include/danet_noise_hip.h) --------
+    @staticmethod
+    def plan_noise(powers, gains, rng, n_src, noise_offsets, noise_lengths, noise_powers, T_max, lo, hi, fft_size,
+                   fft_stride):
+        '''the NoisePlan of one batch.  powers: the STORED mean powers of its rows (groups of n_src consecutive rows
+        are the mixtures), gains: their float32 mix gains or None (= 1), rng: the RandomState the THREE calls draw
+        from, each of size B -- files, positions, SNRs.  noise_offsets / noise_lengths / noise_powers: the noise
+        pool's tables.  Gains in float64, rounded once to float32; 0 for a silent file or a silent mixture'''
+        P = np.asarray(powers, dtype=np.float64).reshape(-1, n_src)
+        B = len(P)
+        g = (np.ones_like(P) if gains is None
+             else np.asarray(gains, dtype=np.float32).astype(np.float64).reshape(-1, n_src))
+        f = rng.randint(0, len(noise_lengths), size=B)
+        u = rng.random_sample(B)
+        snr = rng.uniform(lo, hi, size=B)
+        Lfull = (int(T_max) - 1) * fft_stride
+        offsets, lengths, pads = np.zeros(B, np.int64), np.zeros(B, np.int64), np.zeros(B, np.int64)
+        g64 = np.zeros(B, np.float64)
+        for b in range(B):
+            Ln, off = int(noise_lengths[f[b]]), int(noise_offsets[f[b]])
+            if Ln >= Lfull:               # a segment of exactly T_max frames
+                start = min(int(u[b] * (Ln - Lfull + 1)), Ln - Lfull)
+                offsets[b], lengths[b], pads[b] = off + start, Lfull, 0
+            else:                         # the whole file, placed like a short utterance
+                room = int(T_max) - _stft_frames(Ln, fft_size, fft_stride)
+                offsets[b], lengths[b], pads[b] = off, Ln, min(int(u[b] * (room + 1)), room)
+            P_s = 0.0
+            for c in range(n_src):
+                P_s += float(g[b, c]) * float(g[b, c]) * float(P[b, c])
+            P_n = float(noise_powers[f[b]])
+            if P_s > 0.0 and P_n > 0.0:
+                g64[b] = math.sqrt(P_s / P_n) * 10.0 ** (-float(snr[b]) / 20.0)
+        return NoisePlan(offsets, lengths, pads, g64.astype(np.float32), g64, f.astype(np.int64), snr)
+
+    def noise_stream(self, subset):
+        '''the RandomState the train noise is drawn from, created once (None with the keys null and for `valid` /
+        `test`, which never carry noise)'''
+        if not self.noise_on or subset != 'train':
+            return None
+        if subset not in self._noise_rng:
+            from . import dist
+            self._noise_rng[subset] = np.random.RandomState(
+                [dist.shard_seed(1337), self.SUBSETS.index(subset), 3])
+        return self._noise_rng[subset]
+
     def _pool_key(self, subset):
         return 'test' if (subset == 'valid' and self._alias) else subset
 
@@ -485,6 +627,23 @@ class WavDirData(Dataset):
             rows = self.plan_reverb(len(idx), reverb_rng) if reverb_rng is not None else None
             yield idx, T_max, pads, beg, cnt, gains, speed, rows
 
+    def plan_epoch_noise(self, subset, batch_size, shuffle=False, crop_len=None, crop=False):
+        '''plan_epoch_reverb with a ninth field: None, or -- `train` with NOISE_DIR set -- the NoisePlan of
+        plan_noise, drawn per batch AFTER everything else from a stream of its own (nothing else moves).  Needs the
+        power tables (self.power, self.noise_power: the device half measures them)'''
+        noise_rng = self.noise_stream(subset)
+        C = hparams.MAX_N_SIGNAL
+        if noise_rng is not None and batch_size % C:
+            raise ValueError('wavdir: with NOISE_DIR set the batch size must be a multiple of MAX_N_SIGNAL = %d (got '
+                             '%d): noise is drawn per mixture' % (C, batch_size))
+        for item in self.plan_epoch_reverb(subset, batch_size, shuffle, crop_len, crop):
+            noise = None
+            if noise_rng is not None:
+                noise = self.plan_noise(self.power[self._pool_key(subset)][item[0]], item[5], noise_rng, C,
+                                        self.noise_offsets, self.noise_lengths, self.noise_power, item[1],
+                                        self.noise_snr[0], self.noise_snr[1], hparams.FFT_SIZE, hparams.FFT_STRIDE)
+            yield item + (noise,)
+
     # ---- device half -----------------------------------------------------------------------------
     @staticmethod
     def _device(device=None):
@@ -513,6 +672,19 @@ class WavDirData(Dataset):
             sums = ops.mix_power(pool, self.offsets[subset], self.lengths[subset]).cpu().numpy()
             table = self.power[key] = sums / self.lengths[subset].astype(np.float64)
         return table
+
+    def upload_noise(self, device):
+        '''the float32 noise pool on `device` (uploaded once) and, measured on it once, every noise file's float64
+        mean power over its whole length (ops.mix_power)'''
+        import torch
+        pool = self._noise_pool_dev.get(str(device))
+        if pool is None:
+            pool = self._noise_pool_dev[str(device)] = torch.from_numpy(self.noise_pool_host).to(device)
+        if self.noise_power is None:
+            from . import ops
+            sums = ops.mix_power(pool, self.noise_offsets, self.noise_lengths).cpu().numpy()
+            self.noise_power = sums / self.noise_lengths.astype(np.float64)
+        return pool
 
     def speed_table_on(self, device):
         '''the filter table of the key's P on `device` (float64 numpy rounded once, uploaded once per dataset)'''
@@ -589,9 +761,12 @@ class WavDirData(Dataset):
         from . import ops
         device = self._device(device)
         pool, window = self.upload_pool(subset, device), self._window_on(device)
-        if self.mix_on:
+        noisy = self.noise_on and subset == 'train'
+        if self.mix_on or noisy:
             self.power_table(subset, pool)
-        for idx, T_max, pads, _beg, _cnt, gains, speed, rows in self.plan_epoch_reverb(subset, batch_size, shuffle):
+        noise_pool = self.upload_noise(device) if noisy else None
+        for idx, T_max, pads, _beg, _cnt, gains, speed, rows, noise in self.plan_epoch_noise(subset, batch_size,
+                                                                                             shuffle):
             src, offsets, lengths = pool, self.offsets[subset][idx], self.lengths[subset][idx]
             if speed is not None:         # resampled into a scratch buffer the STFT then reads
                 src, stride = self._take_scratch(device, subset, batch_size)
@@ -611,6 +786,14 @@ class WavDirData(Dataset):
                                      t_begin=0, t_count=T_max)
             if gains is not None:
                 ops.mix_scale_(spectra, torch.from_numpy(gains).to(device))
+            if noise is not None:         # all T_max frames of the noise, scaled: the single rounding fl(g * n)
+                ndesc = ops.prep_desc(noise.offsets, noise.lengths, noise.pads, T_max, noise_pool.numel(),
+                                      hparams.FFT_SIZE, hparams.FFT_STRIDE)
+                nspec = ops.stft_batch(noise_pool, ndesc, T_max, window, hparams.FFT_SIZE, hparams.FFT_STRIDE,
+                                       t_begin=0, t_count=T_max)
+                ops.mix_scale_(nspec, torch.from_numpy(noise.gains).to(device))
+                yield (spectra.cpu().numpy(), nspec.cpu().numpy())
+                continue
             yield (spectra.cpu().numpy(),)
 
     def _take_ring(self, device, n_utt):
@@ -621,6 +804,8 @@ class WavDirData(Dataset):
             row += ops.SPEED_DESC_DTYPE.itemsize                            # + one speed descriptor
         if self.reverb_rt60 is not None:
             row += ops.REVERB_DESC_DTYPE.itemsize                           # + one reverb descriptor
+        if self.noise_on:
+            row += ops.PREP_DESC_DTYPE.itemsize + 4 + 8     # per MIXTURE a noise descriptor and a gain (+ alignment)
         ring = self._ring.get(str(device))
         if ring is None or ring['n_utt'] < n_utt or ring['row'] < row:
             slots = []
@@ -642,18 +827,23 @@ class WavDirData(Dataset):
         without a host wait.  Everything is enqueued on the
         stream that is current in the consumer.  LIFETIME: a yielded tensor is a view of one of
         OUT_DEPTH reused device buffers and stays valid until the consumer has asked for OUT_DEPTH - 1
-        more batches (the same rule as feed.BatchFeed; clone it to keep it longer).'''
+        more batches (the same rule as feed.BatchFeed; clone it to keep it longer).  `train` with NOISE_DIR set: one
+        more launch per batch, and what is yielded is a feed.NoisyBatch(src, noise [B, T', F], gains [B]) whose
+        three tensors live by the same rule.'''
         if not self.is_loaded:
             raise RuntimeError('Dataset is not loaded.')
         device = self._device(device)
         F, B, C = hparams.FEATURE_SIZE, hparams.BATCH_SIZE, hparams.MAX_N_SIGNAL
         assert batch_size == B * C, (batch_size, B, C)
         pool, window = self.upload_pool(subset, device), self._window_on(device)
-        if self.mix_on:
+        noisy = self.noise_on and subset == 'train'
+        if self.mix_on or noisy:
             self.power_table(subset, pool)
+        if noisy:
+            self.upload_noise(device)
         ring = self._take_ring(device, batch_size)
-        for idx, T_max, pads, beg, cnt, gains, speed, rows in self.plan_epoch_reverb(subset, batch_size, shuffle,
-                                                                                     crop_len, crop=True):
+        for idx, T_max, pads, beg, cnt, gains, speed, rows, noise in self.plan_epoch_noise(subset, batch_size, shuffle,
+                                                                                           crop_len, crop=True):
             more = {}
             if gains is not None:
                 more['gains'] = gains
@@ -661,15 +851,24 @@ class WavDirData(Dataset):
                 more['speed'] = speed
             if rows is not None:
                 more['reverb'] = rows
+            if noise is not None:         # one more launch; the front-end adds the noise (feed.NoisyBatch)
+                from . import feed
+                out, nout, ngains = self._emit(device, pool, window, ring, subset, idx, T_max, pads, beg, cnt,
+                                               noise=noise, **more)
+                yield feed.NoisyBatch(out.view(B, C, cnt, F), nout, ngains)
+                continue
             out = self._emit(device, pool, window, ring, subset, idx, T_max, pads, beg, cnt, **more)
             yield out.view(B, C, cnt, F)
 
     def _emit(self, device, pool, window, ring, subset, idx, T_max, pads, beg, cnt, gains=None, speed=None,
-              reverb=None):
+              reverb=None, noise=None):
         '''the device half of one batch: descriptor table (and the speed descriptors, the reverb descriptors and
         the gains behind it, in the same copy) through the pinned ring, (one launch that resamples the batch into
         a scratch waveform buffer, one that convolves the samples the cropped frames read into another,) one
-        launch into the next output buffer (and one that scales it in place) -> complex64 [batch, cnt, F]'''
+        launch into the next output buffer (and one that scales it in place) -> complex64 [batch, cnt, F].
+        noise (a NoisePlan): its descriptors and gains ride behind the mix gains in the same copy, and one more STFT
+        launch over the noise pool writes the same frames of the noise into the next of OUT_DEPTH noise buffers
+        -> (that batch, noise complex64 [mixtures, cnt, F], float32 device gains [mixtures])'''
         import torch
         from . import ops
         N, S, F = hparams.FFT_SIZE, hparams.FFT_STRIDE, hparams.FEATURE_SIZE
@@ -702,6 +901,16 @@ class WavDirData(Dataset):
             at, sent = sent, sent + batch_size * 4
             slot.pin[at:sent].numpy().view(np.float32)[:] = gains
             dev_gains = slot.dev[at:sent].view(torch.float32)
+        if noise is not None:             # 24-byte rows (8-byte aligned) and float32 [mixtures] behind everything
+            noise_pool, n_mix = self.upload_noise(device), len(noise.gains)
+            at = (sent + 7) & ~7
+            sent = at + n_mix * row
+            ops.prep_desc(noise.offsets, noise.lengths, noise.pads, T_max, noise_pool.numel(), N, S,
+                          out=slot.pin[at:sent].numpy().view(ops.PREP_DESC_DTYPE))
+            dev_noise_table = slot.dev[at:sent]
+            at, sent = sent, sent + n_mix * 4
+            slot.pin[at:sent].numpy().view(np.float32)[:] = noise.gains
+            dev_noise_gains = slot.dev[at:sent].view(torch.float32)
         slot.dev[:sent].copy_(slot.pin[:sent], non_blocking=True)
         slot.event.record(torch.cuda.current_stream(device))
         slot.used = True
@@ -718,4 +927,13 @@ class WavDirData(Dataset):
         ops.stft_batch(src, dev_table, T_max, window, N, S, t_begin=beg, t_count=cnt, out=out)
         if gains is not None:
             ops.mix_scale_(out, dev_gains)
+        if noise is not None:
+            nring = ring.setdefault('noise_out', [None] * self.OUT_DEPTH)
+            n = n_mix * cnt * F
+            nbuf = nring[k % self.OUT_DEPTH]
+            if nbuf is None or nbuf.numel() < n:
+                nbuf = nring[k % self.OUT_DEPTH] = torch.empty(n, dtype=torch.complex64, device=device)
+            nout = nbuf[:n].view(n_mix, cnt, F)
+            ops.stft_batch(noise_pool, dev_noise_table, T_max, window, N, S, t_begin=beg, t_count=cnt, out=nout)
+            return out, nout, dev_noise_gains
         return out

@@ -26,6 +26,7 @@ shares a queue with the main or the side stream and the step is 1 ms slower -- t
 the existing side stream, which is idle during the forward pass); device buffers from the caching
 allocator (`record_stream`: re-allocation and event polling every step).
 '''
+import collections
 import inspect
 from random import randint
 
@@ -33,6 +34,25 @@ import numpy as np
 import torch
 
 from .hparams import hparams
+
+
+# what a feed yields instead of a tensor when the mixture has a component that is not a target (the wavdir dataset
+# with NOISE_DIR set): src complex64 [B, C, T', F], noise complex64 [B, T', F], gain float32 [B] or None (the noise
+# is already scaled); cli.train_epoch unpacks it into Model.train_step(src, s_noise=noise, s_noise_gain=gain)
+NoisyBatch = collections.namedtuple('NoisyBatch', 'src noise gain')
+
+
+def _noisy_batch_host(data_pt, crop_len=None):
+    '''to_batch_host for a data point with a second element, the noise [B, T, F]: -> numpy views ([B, C, T', F],
+    [B, T', F]), both cut by the ONE crop that is drawn (the draw to_batch_host makes)'''
+    a = np.asarray(data_pt[0])
+    a = a.reshape(hparams.BATCH_SIZE, hparams.MAX_N_SIGNAL, -1, hparams.FEATURE_SIZE)
+    nz = np.asarray(data_pt[1]).reshape(hparams.BATCH_SIZE, -1, hparams.FEATURE_SIZE)
+    assert nz.shape[1] == a.shape[2], (nz.shape, a.shape)
+    if crop_len is not None and a.shape[2] > crop_len:
+        beg = randint(0, a.shape[2] - crop_len - 1)                       # main.py:424-425
+        a, nz = a[:, :, beg:beg + crop_len], nz[:, beg:beg + crop_len]
+    return a, nz
 
 
 def to_batch_host(data_pt, crop_len=None):
@@ -51,20 +71,30 @@ class _Slot(object):
     upload through them, and the event behind the last step that read the device buffer.  The
     two events are created once and re-recorded (no event object is created or destroyed per
     step: every runtime allocation inside the loop is a chance for the one-off stall of DESIGN 5)'''
-    __slots__ = ('buf', 'dev', 'event', 'consumed', 'uploaded', 'read')
+    __slots__ = ('buf', 'dev', 'event', 'consumed', 'uploaded', 'read', 'split')
 
     def __init__(self):
         self.buf, self.dev, self.event, self.consumed = None, None, None, None
         self.uploaded = self.read = False      # has `event` / `consumed` been recorded yet
+        self.split = None                      # (src shape, noise shape) of a staged noisy batch
 
-    def stage(self, a, pin=True):
-        n = int(np.prod(a.shape))
+    def stage(self, a, pin=True, noise=None):
+        '''noise: a second array staged right behind `a` -- the flat tensor of both is returned, and `split` says
+        where one ends'''
+        n = int(np.prod(a.shape)) + (int(np.prod(noise.shape)) if noise is not None else 0)
         if self.uploaded:
             self.event.synchronize()           # the previous H2D copy out of this slot is done
         if self.buf is None or self.buf.numel() < n:
             self.buf = torch.empty(max(n, 1), dtype=torch.complex64)
             if pin:
                 self.buf = self.buf.pin_memory()
+        if noise is not None:
+            na = int(np.prod(a.shape))
+            t, self.split = self.buf[:n], (tuple(a.shape), tuple(noise.shape))
+            np.copyto(t[:na].view(*a.shape).numpy(), a, casting='same_kind')
+            np.copyto(t[na:].view(*noise.shape).numpy(), noise, casting='same_kind')
+            return t
+        self.split = None
         t = self.buf[:n].view(*a.shape)
         np.copyto(t.numpy(), a, casting='same_kind')      # cast + crop + gather in one pass
         return t
@@ -87,6 +117,9 @@ def _take_slots(key, depth):
 
 class BatchFeed(object):
     '''for spectra in BatchFeed(dataset.epoch(...), device, crop_len): model.train_step(spectra)
+
+    A data point with a second element -- the noise, numpy [B, T, F] -- goes through the same slot and the same
+    upload, cut by the same crop, and comes out as NoisyBatch(src, noise, None).
 
     Yields complex64 [B, C, T', F] tensors on `device`, already ordered behind their upload on
     the stream that is current in the consumer.  A yielded tensor is a view of one of `depth`
@@ -124,9 +157,15 @@ class BatchFeed(object):
 
     def _stage(self, data_pt):
         '''host batch -> (pinned staging tensor, its slot); draws the crop offset'''
-        a = to_batch_host(data_pt, self.crop_len)
+        noise = None
+        if len(data_pt) > 1:                    # (sources, noise): one slot, one upload, one crop
+            a, noise = _noisy_batch_host(data_pt, self.crop_len)
+        else:
+            a = to_batch_host(data_pt, self.crop_len)
         slot = self.slots[self._k % self.depth]
         self._k += 1
+        if noise is not None:
+            return slot.stage(a, pin=self.cuda, noise=noise), slot
         return slot.stage(a, pin=self.cuda), slot
 
     def _upload(self, t, slot):
@@ -153,6 +192,10 @@ class BatchFeed(object):
             torch.cuda.current_stream(self.device).wait_event(slot.event)
         self._out = slot
         self.n += 1
+        if slot.split is not None:              # the sources first, the noise behind them: both views contiguous
+            shape, nshape = slot.split
+            na = int(np.prod(shape))
+            return NoisyBatch(d[:na].view(shape), d[na:].view(nshape), None)
         return d
 
     def _consumed(self):
@@ -166,6 +209,13 @@ class BatchFeed(object):
     def __iter__(self):
         if self.mode == 'sync':
             for data_pt in self.source:
+                if len(data_pt) > 1:
+                    a, nz = _noisy_batch_host(data_pt, self.crop_len)
+                    both = np.concatenate([np.ravel(a), np.ravel(nz)]).astype(np.complex64)
+                    self.n += 1
+                    d = torch.as_tensor(both).to(self.device)
+                    yield NoisyBatch(d[:a.size].view(a.shape), d[a.size:].view(nz.shape), None)
+                    continue
                 a = to_batch_host(data_pt, self.crop_len)
                 self.n += 1
                 yield torch.as_tensor(np.ascontiguousarray(a).astype(np.complex64)).to(self.device)

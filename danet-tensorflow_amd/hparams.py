@@ -25,6 +25,9 @@ unchanged.  Differences, all deliberate:
   resample every utterance of every train batch by a drawn speed factor; every other dataset ignores it.
 * `REVERB_RT60_MAX` (seconds in [0, 1.0], default None = off) makes the `wavdir` dataset convolve every
   utterance of every train batch with a drawn synthetic room response; every other dataset ignores it.
+* `NOISE_DIR` (a folder of noise recordings) with `NOISE_SNR_MIN` / `NOISE_SNR_MAX` (dB, -30 <= min <= max <= 60;
+  all three default None = off) make the `wavdir` dataset add a drawn segment of a drawn noise file to every train
+  mixture at a drawn SNR, the targets staying clean; every other dataset ignores them.
 * `EVAL_SI_SDR` (true / false, default None = off) makes `Model.valid_step` return `SI-SDR` and `SI-SDRi` of the
   separated waveforms next to `loss` and `SNR`, for every dataset; `train_step` and `infer` never compute it.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
@@ -89,6 +92,12 @@ DEFAULTS = {
     # `valid` / `test` also report the SI-SDR of the separated waveforms and its improvement over the mixture, dB:
     # true = on, null / false = off (not in the reference; include/danet_metric_hip.h)
     'EVAL_SI_SDR': None,
+    # additive noise in the `wavdir` dataset's train subset: a folder of noise recordings (NOISE_DIR/**/*.wav) and the
+    # range the SNR of every mixture is drawn from, dB in [-30, 60]; all three None = off (not in the reference;
+    # include/danet_noise_hip.h)
+    'NOISE_DIR': None,
+    'NOISE_SNR_MIN': None,
+    'NOISE_SNR_MAX': None,
 }
 
 

@@ -54,6 +54,7 @@ class Model(object):
         self.seed = int(seed)
         self._gen = torch.Generator().manual_seed(seed)
         self._dropout = None
+        self._noise = None          # (s_noise, s_noise_gain) while forward_noisy() builds its forward pass
         self._flat = None
         self.learn_rate = float(hparams.LR)
         self.step_count = 0
@@ -320,7 +321,10 @@ class Model(object):
         unfused path.'''
         B, E = hparams.BATCH_SIZE, hparams.EMBED_SIZE
         eps = float(hparams.EPS)
-        fe = ops.frontend(s_src_signals)                       # main.py:233-240
+        if self._noise is None:
+            fe = ops.frontend(s_src_signals)                   # main.py:233-240
+        else:                                                  # (forward_noisy)
+            fe = ops.noise_frontend(s_src_signals, *self._noise)
         self._dropout = None
         if s_dropout_keep < 1.0:
             s_embed = self.encoder(fe['mix_log'], s_dropout_keep)
@@ -365,6 +369,17 @@ class Model(object):
         out['mix_pwr'] = fe['mix_pwr']
         return out
 
+    def forward_noisy(self, s_src_signals, s_noise, s_noise_gain=None, **kw):
+        '''forward(s_src_signals, **kw) over a mixture with a component that is not a target (the wavdir dataset's
+        NOISE_DIR): s_noise complex64 [B, T, F], s_noise_gain float32 [B] or None (= 1).  ops.noise_frontend
+        replaces ops.frontend and nothing else changes: encoder, estimators, separator and loss see the noisy
+        mixture, and the targets stay the CLEAN sources.  (A method of its own: forward() keeps its signature.)'''
+        self._noise = (s_noise, s_noise_gain)
+        try:
+            return self.forward(s_src_signals, **kw)
+        finally:
+            self._noise = None
+
     def debug_fetch(self, s_src_signals):
         '''the `-m debug` fetch list (main.py:387-397): embed, attrs, input,
         output (+ module debug_fetches when hparams.DEBUG)'''
@@ -377,10 +392,11 @@ class Model(object):
         return res
 
     # ------------------------------------------------------------ train step
-    def train_step(self, s_src_signals, sync_metrics=True):
+    def train_step(self, s_src_signals, sync_metrics=True, s_noise=None, s_noise_gain=None):
         '''one `g_sess.run(train_fetches)` (main.py:430-431): forward, backward,
         gradient all-reduce, value clip, Adam.  Returns dict(loss, SNR, LR) of
-        device scalars (no host sync unless the caller reads them).'''
+        device scalars (no host sync unless the caller reads them).  s_noise / s_noise_gain: the step trains on
+        the mixture of the sources and that noise against the clean sources (forward_noisy); None: today's step.'''
         # bounded run-ahead + status of the steps that have completed (raises DanetHipError
         # at most ops.MAX_STEPS_IN_FLIGHT steps after a hand-off timeout)
         ops.poll_status(self.device)
@@ -389,8 +405,12 @@ class Model(object):
         chain = ops.heads_chain()        # small finalize kernels go to the side stream (ops.py)
         chain.__enter__()
         try:
-            out = self.forward(s_src_signals, fuse_heads=self.fuse_heads,
-                               s_dropout_keep=float(hparams.DROPOUT_KEEP_PROB))    # main.py:429
+            if s_noise is None:
+                out = self.forward(s_src_signals, fuse_heads=self.fuse_heads,
+                                   s_dropout_keep=float(hparams.DROPOUT_KEEP_PROB))    # main.py:429
+            else:
+                out = self.forward_noisy(s_src_signals, s_noise, s_noise_gain, fuse_heads=self.fuse_heads,
+                                         s_dropout_keep=float(hparams.DROPOUT_KEEP_PROB))
         except BaseException:
             chain.__exit__(None, None, None)
             ops.drop_lazy(self.device)     # this step's queued finalizers must not run in the next

@@ -324,6 +324,38 @@ def frontend(src, want_phase=False, want_mix=False):
     return out
 
 
+def noise_frontend(src, noise, gain=None, want_mix=False):
+    '''ops.frontend over the mixture of the C sources and one more component that is not a target
+    (danet_noise_frontend_fwd, include/danet_noise_hip.h): mixture = sum of the sources + fl(gain[b] * noise),
+    ONE launch.  src complex64 [B,C,T,F], noise complex64 [B,T,F], gain float32 [B] or None (= 1), all contiguous
+    on one device -> the dict of ops.frontend: src_pwr [B,C,T,F] (the clean sources'), mix_pwr, mix_log [B,T,F],
+    phasor [B,T,F,2], and mix complex64 [B,T,F] when asked.  On the extension library libdanet_noise_hip.so,
+    mapped at the first call: a run with NOISE_DIR null never gets here.'''
+    assert src.is_cuda and src.dtype == torch.complex64 and src.dim() == 4 and src.is_contiguous(), \
+        (src.device, src.dtype, src.shape)
+    B, C, T, F = src.shape
+    assert noise.dtype == torch.complex64 and noise.device == src.device and tuple(noise.shape) == (B, T, F) \
+        and noise.is_contiguous(), (noise.device, noise.dtype, noise.shape)
+    if gain is not None:
+        assert gain.dtype == torch.float32 and gain.device == src.device and tuple(gain.shape) == (B,) \
+            and gain.is_contiguous(), (gain.device, gain.dtype, gain.shape)
+    dev = src.device
+    out = dict(
+        src_pwr=torch.empty(B, C, T, F, device=dev),
+        mix_pwr=torch.empty(B, T, F, device=dev),
+        mix_log=torch.empty(B, T, F, device=dev),
+        phasor=torch.empty(B, T, F, 2, device=dev))
+    mix = torch.empty(B, T, F, dtype=torch.complex64, device=dev) if want_mix else None
+    with _lib.timed('noise_frontend'):
+        _lib.noise_check(_lib.load_noise().danet_noise_frontend_fwd(
+            _lib.stream(), B, C, T * F, ptr(torch.view_as_real(src)), ptr(torch.view_as_real(noise)), ptr(gain),
+            ptr(out['mix_pwr']), ptr(out['mix_log']), ptr(out['phasor']), ptr(out['src_pwr']),
+            ptr(torch.view_as_real(mix)) if mix is not None else None))
+    if want_mix:
+        out['mix'] = mix
+    return out
+
+
 def reattach_phase(sep_pwr, phasor, perm_idx=None):
     '''main.py:281-284 / :330-335 (with the permutation gather of :293-306)'''
     B, C, T, F = sep_pwr.shape
