@@ -1,5 +1,5 @@
 '''
-Builds the nine HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the ten HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -13,6 +13,7 @@ Builds the nine HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_reverb_hip.so        csrc/reverb/*.hip        include/danet_reverb_hip.h
     libdanet_metric_hip.so        csrc/metric/*.hip        include/danet_metric_hip.h
     libdanet_noise_hip.so         csrc/noise/*.hip         include/danet_noise_hip.h
+    libdanet_level_hip.so         csrc/level/*.hip         include/danet_level_hip.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -65,9 +66,11 @@ REVERB_LIB = REVERB.out
 # build() and then over EXTENSIONS, and nothing pins the length of this tuple
 METRIC = _extension('metric')
 NOISE = _extension('noise')
-EXTENSIONS = (METRIC, NOISE)
+LEVEL = _extension('level')
+EXTENSIONS = (METRIC, NOISE, LEVEL)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out
+LEVEL_LIB = LEVEL.out
 
 
 def _sources(src_dir):
@@ -167,6 +170,10 @@ def build_metric(force=False, verbose=True):
 
 def build_noise(force=False, verbose=True):
     return _build_spec(NOISE, force, verbose)
+
+
+def build_level(force=False, verbose=True):
+    return _build_spec(LEVEL, force, verbose)
 
 
 def build_variant(name, defs):

@@ -1,6 +1,6 @@
 '''
-ctypes binding of the nine HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
-libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric and noise extension libraries.  Each is described
+ctypes binding of the ten HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise and level extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES or EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -18,6 +18,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 
 c_int, c_i64, c_f32, c_sz, c_p, c_u32 = (ctypes.c_int, ctypes.c_int64, ctypes.c_float,
                                          ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32)
+c_f64 = ctypes.c_double
 
 
 class GemmPack(ctypes.Structure):
@@ -195,8 +196,16 @@ NOISE_PROTOTYPES = {
     'danet_noise_frontend_fwd': (c_int, [c_p, c_int, c_int, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_level_hip.h
+LEVEL_PROTOTYPES = {
+    'danet_level_abi_version': (c_int, []),
+    'danet_level_last_error': (ctypes.c_char_p, []),
+    'danet_level_workspace_bytes': (c_sz, [c_int, c_i64]),
+    'danet_level_activity': (c_int, [c_p, c_int, c_p, c_i64, c_p, c_p, c_i64, c_f64, c_i64, c_p, c_p, c_p, c_sz]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Nine shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Ten shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -251,7 +260,12 @@ METRIC = Library('metric', 'libdanet_metric_hip.so', 'METRIC_LIB_PATH', '_metric
 NOISE_ABI_VERSION = 1
 NOISE = Library('noise', 'libdanet_noise_hip.so', 'NOISE_LIB_PATH', '_noise', NOISE_PROTOTYPES,
                 NOISE_ABI_VERSION, 'danet_noise_', 'NOISE_DIR needs the HIP extension library')
-EXTENSIONS = (METRIC, NOISE)
+# loaded when the first power table of a wavdir dataset with MIX_LEVEL_MEASURE = "active" is measured only
+# (ops.level_activity): a run with the key null never maps it
+LEVEL_ABI_VERSION = 1
+LEVEL = Library('level', 'libdanet_level_hip.so', 'LEVEL_LIB_PATH', '_level', LEVEL_PROTOTYPES,
+                LEVEL_ABI_VERSION, 'danet_level_', 'MIX_LEVEL_MEASURE needs the HIP extension library')
+EXTENSIONS = (METRIC, NOISE, LEVEL)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -263,7 +277,8 @@ SPEED_LIB_PATH = os.path.join(_CSRC, SPEED.so)
 REVERB_LIB_PATH = os.path.join(_CSRC, REVERB.so)
 METRIC_LIB_PATH = os.path.join(_CSRC, METRIC.so)
 NOISE_LIB_PATH = os.path.join(_CSRC, NOISE.so)
-_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = None
+LEVEL_LIB_PATH = os.path.join(_CSRC, LEVEL.so)
+_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = None
 _lock = threading.Lock()
 
 
@@ -405,6 +420,17 @@ def load_noise():
 def noise_check(rc):
     if rc != 0:
         _check(NOISE, rc)
+
+
+def load_level():
+    if _level is not None:
+        return _level
+    return _load(LEVEL)
+
+
+def level_check(rc):
+    if rc != 0:
+        _check(LEVEL, rc)
 
 
 # ---- switches ------------------------------------------------------------------

@@ -223,7 +223,20 @@ class WavDirData(Dataset):
     hands the three to ops.noise_frontend in place of ops.frontend -- the targets stay the clean sources.  The
     24-byte noise descriptors and the gains ride in the pinned ring behind the mix gains.  epoch() yields
     (spectra, noise) with the noise already scaled (ops.mix_scale_: the same single rounding), so both routes give
-    the same mixture bit for bit.'''
+    the same mixture bit for bit.
+
+    ACTIVE SPEECH LEVEL (hparams.MIX_LEVEL_MEASURE = "active", default None = mean power: no launch, no allocation,
+    libdanet_level_hip.so not mapped, every batch bit for bit what it is without the key).  Needs MIX_SNR_RANGE or
+    NOISE_DIR: MIX_LEVEL_RANGE alone uses no power.  `train`, `valid` and `test` alike: when a subset's power table
+    is measured -- once per pool, an aliased `valid` sharing `test`'s -- ops.mix_power is followed by ONE pass of
+    ops.level_activity over the same pool (in launches of rows of similar length whose workspace stays under
+    LEVEL_WS_BYTES: level_chunks), and the table holds every file's ITU-T P.56 active power A_c (the rule
+    include/danet_level_hip.h writes out: the two-stage envelope against 16 thresholds anchored on the file's own
+    rms, 200 ms of hangover, the 15.9 dB margin, finished on the host by active_power) in place of its mean power
+    P_c.  Everything that reads the table
+    -- G and sqrt(G / P_c) of plan_gains, P_s = sum g_c^2 P_c of plan_noise -- then works on active levels.  The
+    noise file's own P_n stays its mean power over its whole length: noise has no pauses to exclude.  With speed
+    or reverb on, the level stays that of the stored file, as P_c does.  No draw is added or moved.'''
     SUBSETS = ('train', 'valid', 'test')
     DESC_DEPTH = 8        # pinned descriptor tables in flight
     OUT_DEPTH = 3         # output buffers: a yielded batch stays valid while the next two are drawn
@@ -244,6 +257,7 @@ class WavDirData(Dataset):
         self.noise_files, self.noise_lengths, self.noise_offsets = [], None, None
         self.noise_pool_host, self.noise_skipped, self.noise_power = None, 0, None
         self._noise_rng, self._noise_pool_dev = {}, {}
+        self.level_key = None       # read from hparams by load_host: None (mean power) or 'active'
         self._alias = False
 
     # ---- host half -------------------------------------------------------------------------------
@@ -356,6 +370,69 @@ class WavDirData(Dataset):
     def noise_on(self):
         return self.noise_dir is not None
 
+    LEVEL_MARGIN_DB = 15.9            # P.56: the active level sits this far above the threshold that defines it
+    LEVEL_WS_BYTES = 64 << 20         # workspace of one ops.level_activity launch of power_table
+
+    @staticmethod
+    def level_measure():
+        '''MIX_LEVEL_MEASURE as None or 'active'; anything else -- a bool, a number, another string -- is a
+        ValueError that names the key, and so is 'active' at an SMPRATE whose 30 ms time constant exceeds the 4096
+        samples include/danet_level_hip.h states its accuracy for'''
+        v = getattr(hparams, 'MIX_LEVEL_MEASURE', None)
+        if v is None:
+            return None
+        if not isinstance(v, str) or v != 'active':
+            raise ValueError('hparams.MIX_LEVEL_MEASURE must be null (mean power over the whole file) or "active" '
+                             '(ITU-T P.56 active speech level), got %r' % (v,))
+        if 0.03 * hparams.SMPRATE > 4096:
+            raise ValueError('hparams.MIX_LEVEL_MEASURE = "active" needs 0.03 * SMPRATE <= 4096 samples '
+                             '(include/danet_level_hip.h), got SMPRATE = %r' % (hparams.SMPRATE,))
+        return v
+
+    @staticmethod
+    def level_params(smprate):
+        '''(g, I) of the level rule at the sampling rate `smprate`: g = exp(-1 / (0.03 fs)), I = ceil(0.2 fs)'''
+        return math.exp(-1.0 / (0.03 * smprate)), int(math.ceil(0.2 * smprate))
+
+    @staticmethod
+    def level_thresholds(powers):
+        '''float64 [n, 16]: c_j = sqrt(P) * 2^(j - 10) of every file's mean power P'''
+        P = np.asarray(powers, dtype=np.float64).reshape(-1)
+        return np.sqrt(P)[:, None] * np.ldexp(1.0, np.arange(16) - 10)[None, :]
+
+    @staticmethod
+    def active_power(sumsq, lengths, counts, thresholds):
+        '''the host finish of the level rule (include/danet_level_hip.h, step 4), numpy float64: sumsq [n] the
+        sums of squares, lengths [n], counts [n, 16] the activity counts a_j against thresholds [n, 16] -> the
+        active powers [n].  The first j with a_j > 0 and A_j - C_j <= M decides: j = 0 gives A_0, a later j the
+        linear interpolation in dB between j - 1 and j; none gives the mean power; a silent file keeps 0'''
+        sumsq = np.asarray(sumsq, dtype=np.float64).reshape(-1)
+        lengths = np.asarray(lengths, dtype=np.float64).reshape(-1)
+        counts = np.asarray(counts).reshape(len(sumsq), -1)
+        thresholds = np.asarray(thresholds, dtype=np.float64).reshape(counts.shape)
+        M = WavDirData.LEVEL_MARGIN_DB
+        out = np.zeros(len(sumsq), dtype=np.float64)
+        for u in range(len(sumsq)):
+            if not sumsq[u] > 0.0:
+                continue
+            out[u] = sumsq[u] / lengths[u]
+            a = counts[u].astype(np.float64)
+            live = a > 0
+            A = 10.0 * np.log10(sumsq[u] / np.where(live, a, 1.0))
+            diff = A - 20.0 * np.log10(thresholds[u])
+            hit = np.nonzero(live & (diff <= M))[0]
+            if not len(hit):
+                continue
+            j = int(hit[0])
+            level = A[0]
+            if j > 0:
+                if not live[j - 1]:       # (cannot happen with ordered thresholds: a_{j-1} >= a_j)
+                    continue
+                w = (diff[j - 1] - M) / (diff[j - 1] - diff[j])
+                level = A[j - 1] + w * (A[j] - A[j - 1])
+            out[u] = 10.0 ** (level / 10.0)
+        return out
+
     def load_noise_host(self, out=None):
         '''discover, decode and resample NOISE_DIR into ONE host pool, exactly like a subset's own files'''
         folder = self.noise_dir
@@ -383,6 +460,11 @@ class WavDirData(Dataset):
         self.speed_range = self.speed_perturb_range()
         self.reverb_rt60 = self.reverb_rt60_max()
         self.noise_dir, self.noise_snr = self.noise_keys()
+        self.level_key = self.level_measure()
+        if self.level_key is not None and self.mix_snr_range is None and self.noise_dir is None:
+            raise ValueError('hparams.MIX_LEVEL_MEASURE = %r would do nothing: no source power is used with both '
+                             'MIX_SNR_RANGE and NOISE_DIR null (MIX_LEVEL_RANGE alone shifts a mixture without '
+                             'measuring it); set one of the two or leave the key null' % (self.level_key,))
         root = hparams.DATASET_DIR
         if root is None:
             raise ValueError('the wavdir dataset needs hparams.DATASET_DIR: the folder that holds '
@@ -664,14 +746,46 @@ class WavDirData(Dataset):
 
     def power_table(self, subset, pool):
         '''float64 mean power of every utterance of the subset, measured on the device once (ops.mix_power on
-        the uploaded pool; an aliased `valid` shares `test`'s table)'''
+        the uploaded pool; an aliased `valid` shares `test`'s table).  With MIX_LEVEL_MEASURE = "active" the table
+        holds the active powers instead (active_table)'''
         key = self._pool_key(subset)
         table = self.power.get(key)
         if table is None:
             from . import ops
             sums = ops.mix_power(pool, self.offsets[subset], self.lengths[subset]).cpu().numpy()
+            if self.level_key is not None:
+                table = self.power[key] = self.active_table(subset, pool, sums)
+                return table
             table = self.power[key] = sums / self.lengths[subset].astype(np.float64)
         return table
+
+    def active_table(self, subset, pool, sums):
+        '''float64 active power of every utterance of the subset from its sums of squares: the thresholds of
+        its mean power, ops.level_activity over the pool -- in the launches of level_chunks; the counts do not depend
+        on how the rows are grouped -- and the host finish'''
+        from . import ops
+        offsets, lengths = self.offsets[subset], self.lengths[subset]
+        g, hang = self.level_params(hparams.SMPRATE)
+        thr = self.level_thresholds(sums / lengths.astype(np.float64))
+        counts = np.zeros((len(lengths), ops.LEVEL_THRESHOLDS), dtype=np.int64)
+        for rows in self.level_chunks(lengths, self.LEVEL_WS_BYTES):
+            counts[rows] = ops.level_activity(pool, offsets[rows], lengths[rows], thr[rows], g, hang).cpu().numpy()
+        return self.active_power(sums, lengths, counts, thr)
+
+    @staticmethod
+    def level_chunks(lengths, ws_bytes):
+        '''the rows of a pool in launches of ops.level_activity whose workspace -- rows x tiles of the LONGEST row
+        of the launch x 208 bytes -- stays under ws_bytes (one row is always taken): index vectors, longest rows
+        first, so that a launch holds rows of similar length'''
+        from . import ops
+        lengths = np.asarray(lengths, dtype=np.int64)
+        order = np.argsort(-lengths, kind='stable')
+        a = 0
+        while a < len(order):
+            tiles = max(1, -(-int(lengths[order[a]]) // ops.LEVEL_TILE))
+            step = max(1, int(ws_bytes) // (tiles * (16 + 12 * ops.LEVEL_THRESHOLDS)))
+            yield order[a:a + step]
+            a += step
 
     def upload_noise(self, device):
         '''the float32 noise pool on `device` (uploaded once) and, measured on it once, every noise file's float64

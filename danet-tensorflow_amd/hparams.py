@@ -28,6 +28,9 @@ unchanged.  Differences, all deliberate:
 * `NOISE_DIR` (a folder of noise recordings) with `NOISE_SNR_MIN` / `NOISE_SNR_MAX` (dB, -30 <= min <= max <= 60;
   all three default None = off) make the `wavdir` dataset add a drawn segment of a drawn noise file to every train
   mixture at a drawn SNR, the targets staying clean; every other dataset ignores them.
+* `MIX_LEVEL_MEASURE` (`"active"`, default None = mean power over the whole file) makes the `wavdir` dataset set
+  `MIX_SNR_RANGE` / `NOISE_SNR_*` levels from every source's ITU-T P.56 active speech level, pauses excluded;
+  every other dataset ignores it.
 * `EVAL_SI_SDR` (true / false, default None = off) makes `Model.valid_step` return `SI-SDR` and `SI-SDRi` of the
   separated waveforms next to `loss` and `SNR`, for every dataset; `train_step` and `infer` never compute it.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
@@ -98,6 +101,9 @@ DEFAULTS = {
     'NOISE_DIR': None,
     'NOISE_SNR_MIN': None,
     'NOISE_SNR_MAX': None,
+    # what a source's level is in the `wavdir` dataset's MIX_SNR_RANGE / NOISE_SNR_* rules: None = its mean power over
+    # the whole file, "active" = its ITU-T P.56 active speech level (not in the reference; include/danet_level_hip.h)
+    'MIX_LEVEL_MEASURE': None,
 }
 
 

@@ -559,6 +559,70 @@ def mix_scale_(batch, gains):
     return batch
 
 
+# ---- active speech level of the wavdir dataset (include/danet_level_hip.h) ---------------------------
+# On the extension library libdanet_level_hip.so, mapped at the first call: a wavdir run with
+# MIX_LEVEL_MEASURE null never gets here.
+LEVEL_THRESHOLDS, LEVEL_TILE = 16, 1024              # DANET_LEVEL_THRESHOLDS, DANET_LEVEL_TILE
+LEVEL_MAX_LEN, LEVEL_MAX_HANG = 1 << 31, 1 << 40
+
+
+def level_activity(pool, offsets, lengths, thresholds, g, hang, max_len=None):
+    '''P.56 activity counts of every row [offset, offset + length) of the float32 device vector `pool`
+    -> int64 DEVICE tensor [n, 16] (danet_level_activity: float64 envelope with the smoothing coefficient `g`,
+    `hang` samples of hangover, counts[u][j] against thresholds[u][j]).
+    offsets, lengths: host integer sequences (validated here: a row outside the pool is a ValueError
+    before any upload or launch) or int64 device tensors the caller has validated (the kernel clamps,
+    and `max_len`, an upper bound of the lengths, must then be given).  thresholds: float64 [n, 16], a host
+    array or a device tensor.  Every violation the host can see is a ValueError raised before any launch.'''
+    assert pool.is_cuda and pool.dtype == torch.float32 and pool.dim() == 1 and pool.is_contiguous()
+    g, hang = float(g), int(hang)
+    if not 0.0 < g < 1.0:
+        raise ValueError('level_activity: g must be inside (0, 1), got %r' % (g,))
+    if not 0 <= hang <= LEVEL_MAX_HANG:
+        raise ValueError('level_activity: hang must be in [0, 2^40] samples, got %r' % (hang,))
+    if not torch.is_tensor(offsets):
+        offsets, lengths = np.asarray(offsets, dtype=np.int64), np.asarray(lengths, dtype=np.int64)
+        if offsets.shape != lengths.shape or offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError('level_activity: offsets and lengths must be two vectors of one length >= 1')
+        bad = np.nonzero((offsets < 0) | (lengths < 0) | (offsets + lengths > pool.numel()))[0]
+        if len(bad):
+            u = int(bad[0])
+            raise ValueError('level_activity: utterance %d [%d, %d) is outside the pool of %d samples'
+                             % (u, offsets[u], offsets[u] + lengths[u], pool.numel()))
+        if max_len is None:
+            max_len = int(lengths.max())
+        offsets, lengths = torch.from_numpy(offsets).to(pool.device), torch.from_numpy(lengths).to(pool.device)
+    if max_len is None:
+        raise ValueError('level_activity: device tables need max_len')
+    max_len = int(max_len)
+    for t in (offsets, lengths):
+        assert t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous()
+    n = offsets.numel()
+    if n < 1 or lengths.numel() != n:
+        raise ValueError('level_activity: offsets and lengths must be two vectors of one length >= 1')
+    if not torch.is_tensor(thresholds):
+        thresholds = torch.from_numpy(np.ascontiguousarray(thresholds, dtype=np.float64)).to(pool.device)
+    if thresholds.dtype != torch.float64 or tuple(thresholds.shape) != (n, LEVEL_THRESHOLDS):
+        raise ValueError('level_activity: thresholds must be float64 [%d, %d], got %s %s'
+                         % (n, LEVEL_THRESHOLDS, thresholds.dtype, tuple(thresholds.shape)))
+    assert thresholds.is_cuda and thresholds.is_contiguous()
+    tiles = max(1, -(-max_len // LEVEL_TILE))
+    if not 0 <= max_len <= LEVEL_MAX_LEN or n * tiles >= 1 << 31:
+        raise ValueError('level_activity: need 0 <= max_len <= 2^31 and rows * tiles per row < 2^31 (got max_len %d, '
+                         '%d rows)' % (max_len, n))
+    L = _lib.load_level()
+    nbytes = L.danet_level_workspace_bytes(n, max_len)
+    if nbytes == ctypes.c_size_t(-1).value:
+        _lib.level_check(-1)
+    # once per pool and as large as a fifth of it: a buffer of the call's own, not the grow-only scratch
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=pool.device)
+    out = torch.empty(n, LEVEL_THRESHOLDS, dtype=torch.int64, device=pool.device)
+    with _lib.timed('level_activity'):
+        _lib.level_check(L.danet_level_activity(_lib.stream(), n, ptr(pool), pool.numel(), ptr(offsets), ptr(lengths),
+                                                max_len, g, hang, ptr(thresholds), ptr(out), ptr(ws), nbytes))
+    return out
+
+
 # ---- speed perturbation of the wavdir dataset (include/danet_speed_hip.h) ----------------------------
 # On the extension library libdanet_speed_hip.so, mapped at the first call: a wavdir run with
 # SPEED_PERTURB_RANGE null never gets here.
