@@ -1,5 +1,5 @@
 '''
-Builds the ten HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the eleven HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -14,6 +14,7 @@ Builds the ten HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_metric_hip.so        csrc/metric/*.hip        include/danet_metric_hip.h
     libdanet_noise_hip.so         csrc/noise/*.hip         include/danet_noise_hip.h
     libdanet_level_hip.so         csrc/level/*.hip         include/danet_level_hip.h
+    libdanet_wavloss_hip.so       csrc/wavloss/*.hip       include/danet_wavloss_hip.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -67,10 +68,12 @@ REVERB_LIB = REVERB.out
 METRIC = _extension('metric')
 NOISE = _extension('noise')
 LEVEL = _extension('level')
-EXTENSIONS = (METRIC, NOISE, LEVEL)
+WAVLOSS = _extension('wavloss')
+EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out
 LEVEL_LIB = LEVEL.out
+WAVLOSS_LIB = WAVLOSS.out
 
 
 def _sources(src_dir):
@@ -174,6 +177,10 @@ def build_noise(force=False, verbose=True):
 
 def build_level(force=False, verbose=True):
     return _build_spec(LEVEL, force, verbose)
+
+
+def build_wavloss(force=False, verbose=True):
+    return _build_spec(WAVLOSS, force, verbose)
 
 
 def build_variant(name, defs):

@@ -1,6 +1,6 @@
 '''
-ctypes binding of the ten HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
-libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise and level extension libraries.  Each is described
+ctypes binding of the eleven HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level and wavloss extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES or EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -204,8 +204,16 @@ LEVEL_PROTOTYPES = {
     'danet_level_activity': (c_int, [c_p, c_int, c_p, c_i64, c_p, c_p, c_i64, c_f64, c_i64, c_p, c_p, c_p, c_sz]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_wavloss_hip.h
+WAVLOSS_PROTOTYPES = {
+    'danet_wavloss_abi_version': (c_int, []),
+    'danet_wavloss_last_error': (ctypes.c_char_p, []),
+    'danet_wavloss_fwd': (c_int, [c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    'danet_wavloss_bwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Ten shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Eleven shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -265,7 +273,12 @@ NOISE = Library('noise', 'libdanet_noise_hip.so', 'NOISE_LIB_PATH', '_noise', NO
 LEVEL_ABI_VERSION = 1
 LEVEL = Library('level', 'libdanet_level_hip.so', 'LEVEL_LIB_PATH', '_level', LEVEL_PROTOTYPES,
                 LEVEL_ABI_VERSION, 'danet_level_', 'MIX_LEVEL_MEASURE needs the HIP extension library')
-EXTENSIONS = (METRIC, NOISE, LEVEL)
+# loaded at the first train step (or forward pass with the train branch) of a model built with TRAIN_LOSS = "si-sdr"
+# only (ops.si_sdr_loss): a run with the key null or "pit-mse" never maps it
+WAVLOSS_ABI_VERSION = 1
+WAVLOSS = Library('wavloss', 'libdanet_wavloss_hip.so', 'WAVLOSS_LIB_PATH', '_wavloss', WAVLOSS_PROTOTYPES,
+                  WAVLOSS_ABI_VERSION, 'danet_wavloss_', 'TRAIN_LOSS = "si-sdr" needs the HIP extension library')
+EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -278,7 +291,8 @@ REVERB_LIB_PATH = os.path.join(_CSRC, REVERB.so)
 METRIC_LIB_PATH = os.path.join(_CSRC, METRIC.so)
 NOISE_LIB_PATH = os.path.join(_CSRC, NOISE.so)
 LEVEL_LIB_PATH = os.path.join(_CSRC, LEVEL.so)
-_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = None
+WAVLOSS_LIB_PATH = os.path.join(_CSRC, WAVLOSS.so)
+_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = None
 _lock = threading.Lock()
 
 
@@ -431,6 +445,17 @@ def load_level():
 def level_check(rc):
     if rc != 0:
         _check(LEVEL, rc)
+
+
+def load_wavloss():
+    if _wavloss is not None:
+        return _wavloss
+    return _load(WAVLOSS)
+
+
+def wavloss_check(rc):
+    if rc != 0:
+        _check(WAVLOSS, rc)
 
 
 # ---- switches ------------------------------------------------------------------

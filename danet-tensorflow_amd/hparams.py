@@ -33,6 +33,8 @@ unchanged.  Differences, all deliberate:
   every other dataset ignores it.
 * `EVAL_SI_SDR` (true / false, default None = off) makes `Model.valid_step` return `SI-SDR` and `SI-SDRi` of the
   separated waveforms next to `loss` and `SNR`, for every dataset; `train_step` and `infer` never compute it.
+* `TRAIN_LOSS` (`"pit-mse"` / `"si-sdr"`, default None = `"pit-mse"`) chooses what `Model.train_step` minimises: the
+  reference's PIT-MSE on complex spectra, or minus the SI-SDR (dB) of the separated waveforms; validation is untouched.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -104,6 +106,9 @@ DEFAULTS = {
     # what a source's level is in the `wavdir` dataset's MIX_SNR_RANGE / NOISE_SNR_* rules: None = its mean power over
     # the whole file, "active" = its ITU-T P.56 active speech level (not in the reference; include/danet_level_hip.h)
     'MIX_LEVEL_MEASURE': None,
+    # what Model.train_step minimises: None / "pit-mse" = the reference's PIT-MSE on complex spectra, "si-sdr" = minus
+    # the SI-SDR of the separated waveforms in dB (not in the reference; include/danet_wavloss_hip.h)
+    'TRAIN_LOSS': None,
 }
 
 

@@ -69,6 +69,8 @@ class Model(object):
         self.keep_grads = False
         # train_step: separator + PIT loss as one fused kernel pair (DANET_FUSE_HEADS=0: off)
         self.fuse_heads = os.environ.get('DANET_FUSE_HEADS', '1') == '1'
+        # what train_step minimises: build() sets it from hparams.TRAIN_LOSS ('pit-mse' or 'si-sdr')
+        self.train_loss = 'pit-mse'
 
     # ------------------------------------------------------------ variables
     def get_variable(self, name, shape, init):
@@ -110,6 +112,8 @@ class Model(object):
         '''create sub-modules (main.py:210-211, 249-250, 263-270), materialise
         variables with one dry forward, then flatten them for the optimiser.'''
         self.eval_si_sdr = self._check_eval_si_sdr()
+        # 'pit-mse': the reference's PIT-MSE on complex spectra; 'si-sdr': -SI-SDR of the separated waveforms
+        self.train_loss = self._check_train_loss()
         self.encoder = hparams.get_encoder()(self, 'encoder')
         self.estimator = hparams.get_estimator(
             hparams.TRAIN_ESTIMATOR_METHOD)(self, 'train_estimator')
@@ -158,6 +162,33 @@ class Model(object):
         if hparams.MAX_N_SIGNAL > ops.METRIC_MAX_C:
             raise ValueError('EVAL_SI_SDR needs MAX_N_SIGNAL <= %d (got %d)' % (ops.METRIC_MAX_C, hparams.MAX_N_SIGNAL))
         return True
+
+    @staticmethod
+    def _check_train_loss():
+        '''TRAIN_LOSS (null = "pit-mse") -> 'pit-mse' or 'si-sdr'; ValueError naming the key that rules the choice out'''
+        v = getattr(hparams, 'TRAIN_LOSS', None)
+        if v is None:
+            return 'pit-mse'
+        if not isinstance(v, str) or v not in ('pit-mse', 'si-sdr'):
+            raise ValueError('TRAIN_LOSS must be null, "pit-mse" or "si-sdr" (got %r)' % (v,))
+        if v == 'pit-mse':
+            return v
+        N, S = hparams.FFT_SIZE, hparams.FFT_STRIDE
+        if N < 64 or N > 1024 or N & (N - 1):
+            raise ValueError('TRAIN_LOSS = "si-sdr" needs FFT_SIZE to be a power of two in 64..1024 (got FFT_SIZE = %d): '
+                             'the envelope of danet_metric_synth, whose waveforms the loss is taken on' % N)
+        if 2 * S > N:
+            raise ValueError('TRAIN_LOSS = "si-sdr" needs FFT_STRIDE <= FFT_SIZE / 2 (got FFT_STRIDE = %d at FFT_SIZE '
+                             '= %d): beyond half a window the overlap-added squared window can reach 0 at the window '
+                             'edges' % (S, N))
+        if 8 * S < N:
+            raise ValueError('TRAIN_LOSS = "si-sdr" needs FFT_STRIDE >= FFT_SIZE / 8 (got FFT_STRIDE = %d at FFT_SIZE '
+                             '= %d): the frames that overlap one tile of hops must fit in the 64 KiB of LDS the '
+                             'synthesis kernel uses' % (S, N))
+        if hparams.MAX_N_SIGNAL > ops.WAVLOSS_MAX_C:
+            raise ValueError('TRAIN_LOSS = "si-sdr" needs MAX_N_SIGNAL <= %d (got %d)'
+                             % (ops.WAVLOSS_MAX_C, hparams.MAX_N_SIGNAL))
+        return v
 
     def _flatten(self):
         n = sum(self.vars[k].numel() for k in self._order)
@@ -318,7 +349,8 @@ class Model(object):
         kernel forward and ONE backward (ops.SeparatePitFn); the separated magnitudes then
         exist only in registers and `sep_pwr` is not in the returned dict.  Needs a separator
         that exposes its activation (`ACT`, the dot-product separators); others take the
-        unfused path.'''
+        unfused path.  A model built with TRAIN_LOSS = "si-sdr" (`train_loss`) always takes the unfused heads and
+        returns the waveform loss as `loss`, with its own permutation in `loss_perm_idx`.'''
         B, E = hparams.BATCH_SIZE, hparams.EMBED_SIZE
         eps = float(hparams.EPS)
         if self._noise is None:
@@ -337,7 +369,17 @@ class Model(object):
             s_attractors = self.estimator(                     # main.py:251-254
                 s_embed, s_src_pwr=fe['src_pwr'], s_mix_pwr=fe['mix_pwr'])
             act = getattr(self.separator, 'ACT', None)
-            if fuse_heads and act is not None and not hparams.DEBUG and not with_valid:
+            if self.train_loss == 'si-sdr':
+                # the waveform loss needs the separated magnitudes: the unfused heads.  SNR, perm_idx and perms keep
+                # their meaning (one more launch, outside autograd); the loss's own permutation is loss_perm_idx
+                s_sep_pwr = self.separator(fe['mix_pwr'], s_attractors, s_embed_flat)
+                loss, loss_idx = ops.si_sdr_loss(s_src_signals, s_sep_pwr, phasor)
+                with torch.no_grad():
+                    _mse, perms, idx, snr = ops.pit_mse_loss(
+                        s_src_signals, s_sep_pwr.detach(), phasor, mode=0, eps=eps)
+                out.update(attrs=s_attractors, sep_pwr=s_sep_pwr, loss=loss, SNR=snr,
+                           perm_idx=idx, perms=perms, loss_perm_idx=loss_idx)
+            elif fuse_heads and act is not None and not hparams.DEBUG and not with_valid:
                 loss, perms, idx, snr = ops.separate_pit_loss(      # :271-272 + :281-290, 308-309
                     fe['mix_pwr'], s_attractors, s_embed_flat, s_src_signals, phasor, act,
                     mode=0, eps=eps)

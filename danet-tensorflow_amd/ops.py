@@ -926,6 +926,109 @@ def si_sdr(src, est, fft_stride=None):
     return mean2[0], mean2[1], per_utt, perm_idx
 
 
+# ---- waveform training loss (include/danet_wavloss_hip.h) ---------------------------------------------
+# On the extension library libdanet_wavloss_hip.so, mapped at the first call: a run with TRAIN_LOSS null or
+# "pit-mse" never gets here.  Forward: reattach_phase -> metric_synth -> metric_gram (libdanet_metric_hip.so) ->
+# wavloss_fwd; backward: ONE launch, wavloss_bwd.
+WAVLOSS_MAX_C = 4                                    # DANET_WAVLOSS_MAX_C
+
+
+def wavloss_tile_frames(N):
+    '''DANET_WAVLOSS_TILE_FRAMES(N): the frames one workgroup of danet_wavloss_bwd takes'''
+    return min(32, (16384 - 3 * N // 2) // (3 * N // 2))
+
+
+def wavloss_fwd(G, out=None):
+    '''float64 Gram matrices [B, 2C, 2C] -> (loss_f64 [1], loss_f32 [1], per_utt [B], perm_idx int32 [B],
+    pair int32 [B, C], coef float64 [B, C, 2]), ONE launch (danet_wavloss_fwd); out: optional tuple of the six to
+    write into'''
+    assert G.is_cuda and G.dtype == torch.float64 and G.dim() == 3 and G.is_contiguous() and G.shape[1] == G.shape[2]
+    B, M = G.shape[0], G.shape[1]
+    assert M % 2 == 0, M
+    C, dev = M // 2, G.device
+    if out is None:
+        out = (torch.empty(1, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.float32, device=dev),
+               torch.empty(B, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(B, C, dtype=torch.int32, device=dev), torch.empty(B, C, 2, dtype=torch.float64, device=dev))
+    loss64, loss32, per_utt, perm_idx, pair, coef = out
+    with _lib.timed('wavloss_fwd'):
+        _lib.wavloss_check(_lib.load_wavloss().danet_wavloss_fwd(
+            _lib.stream(), B, C, ptr(G), ptr(loss64), ptr(loss32), ptr(per_utt), ptr(perm_idx), ptr(pair), ptr(coef)))
+    return out
+
+
+def wavloss_bwd(wav, pair, coef, fft_size, fft_stride, window=None, dloss=None, phasor=None, out=None):
+    '''the gradient of the waveform loss with respect to the estimates' spectra, ONE launch (danet_wavloss_bwd):
+    wav float32 [B, 2C, (T - 1) * S] (ops.metric_synth), pair int32 [B, C] and coef float64 [B, C, 2]
+    (ops.wavloss_fwd) -> complex64 dX [B, C, T, F], or with phasor float32 [B, T, F, 2] the real float32
+    dsep [B, C, T, F].  dloss: float32 device scalar or None (= 1); window: float32 device vector [N] (default
+    hparams.FFT_WND, uploaded once).'''
+    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.is_contiguous()
+    B, M, Ls = wav.shape
+    N, S = int(fft_size), int(fft_stride)
+    assert M % 2 == 0 and S >= 1 and Ls % S == 0, (M, Ls, S)
+    C, T, F, dev = M // 2, Ls // S + 1, N // 2 + 1, wav.device
+    assert pair.dtype == torch.int32 and pair.is_contiguous() and tuple(pair.shape) == (B, C) and pair.device == dev
+    assert coef.dtype == torch.float64 and coef.is_contiguous() and tuple(coef.shape) == (B, C, 2) and coef.device == dev
+    window = _metric_window(dev) if window is None else _f32(window).contiguous()
+    assert window.numel() == N and window.device == dev, (window.numel(), N)
+    if dloss is not None:
+        assert dloss.dtype == torch.float32 and dloss.numel() == 1 and dloss.device == dev
+    if phasor is not None:
+        assert phasor.dtype == torch.float32 and phasor.is_contiguous() and tuple(phasor.shape) == (B, T, F, 2) \
+            and phasor.device == dev, (phasor.dtype, phasor.shape)
+    if out is None:
+        out = torch.empty(B, C, T, F, dtype=torch.complex64 if phasor is None else torch.float32, device=dev)
+    assert out.is_contiguous() and tuple(out.shape) == (B, C, T, F) and out.device == dev
+    assert out.dtype == (torch.complex64 if phasor is None else torch.float32), out.dtype
+    with _lib.timed('wavloss_bwd'):
+        _lib.wavloss_check(_lib.load_wavloss().danet_wavloss_bwd(
+            _lib.stream(), B, C, T, N, S, ptr(wav), ptr(pair), ptr(coef), ptr(window), ptr(dloss), ptr(phasor),
+            ptr(torch.view_as_real(out)) if phasor is None else ptr(out)))
+    return out
+
+
+class SiSdrLossFn(torch.autograd.Function):
+    '''-SI-SDR (dB) of the separated waveforms under the metric's permutation rule (include/danet_wavloss_hip.h):
+    (src complex64 [B,C,T,F], sep_pwr [B,C,T,F], phasor [B,T,F,2]) -> (loss, perm_idx).  Shaped like PitMseFn: the
+    gradient goes to sep_pwr only, backward is ONE launch.  The waveforms must survive until backward, so they
+    are a tensor of this call's own, not the cached scratch ops.si_sdr shares with valid_step.'''
+
+    @staticmethod
+    def forward(ctx, src, sep_pwr, phasor):
+        from .hparams import hparams
+        assert src.dtype == torch.complex64
+        B, C, T, F = sep_pwr.shape
+        S = int(hparams.FFT_STRIDE)
+        sep_pwr = _f32(sep_pwr.contiguous())
+        phasor = _f32(phasor.contiguous())
+        est = reattach_phase(sep_pwr, phasor)                  # unpermuted: the loss does its own search
+        wav = metric_synth(src, est, S)
+        loss64, loss, _per_utt, perm_idx, pair, coef = wavloss_fwd(metric_gram(wav))
+        ctx.save_for_backward(wav, pair, coef, phasor)
+        ctx.args = (2 * (F - 1), S)
+        ctx.mark_non_differentiable(perm_idx)
+        ctx.set_materialize_grads(False)
+        return loss.view(()), perm_idx
+
+    @staticmethod
+    def backward(ctx, dloss, _dperm):
+        if dloss is None:
+            return None, None, None
+        wav, pair, coef, phasor = ctx.saved_tensors
+        N, S = ctx.args
+        # dloss is a device scalar: the kernel reads it (no host sync, no extra pass)
+        dsep = wavloss_bwd(wav, pair, coef, N, S, dloss=_f32(dloss.contiguous()), phasor=phasor)
+        return None, dsep, None
+
+
+def si_sdr_loss(s_x, s_y_pwr, phasor):
+    '''(loss, loss_perm_idx): minus the SI-SDR in dB of the waveforms of the separated magnitudes `s_y_pwr` with
+    the mixture phase against the references `s_x`, a float32 device scalar, and the index of every utterance's
+    permutation in itertools.permutations order'''
+    return SiSdrLossFn.apply(s_x, s_y_pwr, phasor)
+
+
 # ---------------------------------------------------------------------------
 # LSTM layer (both directions), raw forward / backward on time-major tensors
 # ---------------------------------------------------------------------------
