@@ -1,5 +1,5 @@
 '''
-Builds the eleven HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the twelve HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -15,6 +15,7 @@ Builds the eleven HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_noise_hip.so         csrc/noise/*.hip         include/danet_noise_hip.h
     libdanet_level_hip.so         csrc/level/*.hip         include/danet_level_hip.h
     libdanet_wavloss_hip.so       csrc/wavloss/*.hip       include/danet_wavloss_hip.h
+    libdanet_gclip_hip.so         csrc/gclip/*.hip         include/danet_gclip_hip.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -69,11 +70,13 @@ METRIC = _extension('metric')
 NOISE = _extension('noise')
 LEVEL = _extension('level')
 WAVLOSS = _extension('wavloss')
-EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS)
+GCLIP = _extension('gclip')
+EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out
 LEVEL_LIB = LEVEL.out
 WAVLOSS_LIB = WAVLOSS.out
+GCLIP_LIB = GCLIP.out
 
 
 def _sources(src_dir):
@@ -181,6 +184,10 @@ def build_level(force=False, verbose=True):
 
 def build_wavloss(force=False, verbose=True):
     return _build_spec(WAVLOSS, force, verbose)
+
+
+def build_gclip(force=False, verbose=True):
+    return _build_spec(GCLIP, force, verbose)
 
 
 def build_variant(name, defs):

@@ -1,6 +1,6 @@
 '''
-ctypes binding of the eleven HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
-libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level and wavloss extension libraries.  Each is described
+ctypes binding of the twelve HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss and gclip extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES or EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -212,8 +212,18 @@ WAVLOSS_PROTOTYPES = {
     'danet_wavloss_bwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_gclip_hip.h
+GCLIP_PROTOTYPES = {
+    'danet_gclip_abi_version': (c_int, []),
+    'danet_gclip_last_error': (ctypes.c_char_p, []),
+    'danet_gclip_partials': (c_int, [c_i64]),
+    'danet_gclip_sumsq': (c_int, [c_p, c_i64, c_p, c_p, c_int]),
+    'danet_gclip_adam_step': (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_int,
+                                      c_f64, c_p, c_int, c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Eleven shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Twelve shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -278,7 +288,12 @@ LEVEL = Library('level', 'libdanet_level_hip.so', 'LEVEL_LIB_PATH', '_level', LE
 WAVLOSS_ABI_VERSION = 1
 WAVLOSS = Library('wavloss', 'libdanet_wavloss_hip.so', 'WAVLOSS_LIB_PATH', '_wavloss', WAVLOSS_PROTOTYPES,
                   WAVLOSS_ABI_VERSION, 'danet_wavloss_', 'TRAIN_LOSS = "si-sdr" needs the HIP extension library')
-EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS)
+# loaded at the first train step of a model built with GRAD_CLIP_NORM set only (ops.grad_sumsq): a run with the key
+# null never maps it
+GCLIP_ABI_VERSION = 1
+GCLIP = Library('gclip', 'libdanet_gclip_hip.so', 'GCLIP_LIB_PATH', '_gclip', GCLIP_PROTOTYPES,
+                GCLIP_ABI_VERSION, 'danet_gclip_', 'GRAD_CLIP_NORM needs the HIP extension library')
+EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -292,7 +307,8 @@ METRIC_LIB_PATH = os.path.join(_CSRC, METRIC.so)
 NOISE_LIB_PATH = os.path.join(_CSRC, NOISE.so)
 LEVEL_LIB_PATH = os.path.join(_CSRC, LEVEL.so)
 WAVLOSS_LIB_PATH = os.path.join(_CSRC, WAVLOSS.so)
-_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = None
+GCLIP_LIB_PATH = os.path.join(_CSRC, GCLIP.so)
+_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = _gclip = None
 _lock = threading.Lock()
 
 
@@ -456,6 +472,17 @@ def load_wavloss():
 def wavloss_check(rc):
     if rc != 0:
         _check(WAVLOSS, rc)
+
+
+def load_gclip():
+    if _gclip is not None:
+        return _gclip
+    return _load(GCLIP)
+
+
+def gclip_check(rc):
+    if rc != 0:
+        _check(GCLIP, rc)
 
 
 # ---- switches ------------------------------------------------------------------

@@ -35,6 +35,9 @@ unchanged.  Differences, all deliberate:
   separated waveforms next to `loss` and `SNR`, for every dataset; `train_step` and `infer` never compute it.
 * `TRAIN_LOSS` (`"pit-mse"` / `"si-sdr"`, default None = `"pit-mse"`) chooses what `Model.train_step` minimises: the
   reference's PIT-MSE on complex spectra, or minus the SI-SDR (dB) of the separated waveforms; validation is untouched.
+* `GRAD_CLIP_NORM` (a finite number > 0, default None = off) makes `Model.train_step` scale the whole gradient so that
+  its global L2 norm does not exceed the value (`torch.nn.utils.clip_grad_norm_`'s rule), before the value clip
+  `GRAD_CLIP_THRES`; the step then also returns `grad_norm` and `clip_coef`.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -109,6 +112,9 @@ DEFAULTS = {
     # what Model.train_step minimises: None / "pit-mse" = the reference's PIT-MSE on complex spectra, "si-sdr" = minus
     # the SI-SDR of the separated waveforms in dB (not in the reference; include/danet_wavloss_hip.h)
     'TRAIN_LOSS': None,
+    # the largest global L2 norm of the gradient: beyond it the whole gradient is scaled down to it, ahead of the
+    # value clip GRAD_CLIP_THRES; None = off (not in the reference; include/danet_gclip_hip.h)
+    'GRAD_CLIP_NORM': None,
 }
 
 

@@ -71,6 +71,8 @@ class Model(object):
         self.fuse_heads = os.environ.get('DANET_FUSE_HEADS', '1') == '1'
         # what train_step minimises: build() sets it from hparams.TRAIN_LOSS ('pit-mse' or 'si-sdr')
         self.train_loss = 'pit-mse'
+        self.grad_clip_norm = None
+        self._gclip_partials = None
 
     # ------------------------------------------------------------ variables
     def get_variable(self, name, shape, init):
@@ -114,6 +116,9 @@ class Model(object):
         self.eval_si_sdr = self._check_eval_si_sdr()
         # 'pit-mse': the reference's PIT-MSE on complex spectra; 'si-sdr': -SI-SDR of the separated waveforms
         self.train_loss = self._check_train_loss()
+        # None: off; a float: the largest global L2 norm of the gradient (include/danet_gclip_hip.h)
+        self.grad_clip_norm = self._check_grad_clip_norm()
+        self._gclip_partials = None
         self.encoder = hparams.get_encoder()(self, 'encoder')
         self.estimator = hparams.get_estimator(
             hparams.TRAIN_ESTIMATOR_METHOD)(self, 'train_estimator')
@@ -189,6 +194,21 @@ class Model(object):
             raise ValueError('TRAIN_LOSS = "si-sdr" needs MAX_N_SIGNAL <= %d (got %d)'
                              % (ops.WAVLOSS_MAX_C, hparams.MAX_N_SIGNAL))
         return v
+
+    @staticmethod
+    def _check_grad_clip_norm():
+        '''GRAD_CLIP_NORM (null: off) -> None or a float; ValueError naming the key'''
+        v = getattr(hparams, 'GRAD_CLIP_NORM', None)
+        if v is None:
+            return None
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError('GRAD_CLIP_NORM must be null or a number > 0 (got %r)' % (v,))
+        if not math.isfinite(v) or v <= 0:
+            raise ValueError('GRAD_CLIP_NORM must be null or a finite number > 0 (got %r)' % (v,))
+        if _lib.expert('early_adam', False):
+            raise ValueError('GRAD_CLIP_NORM cannot be combined with the expert setting early_adam: the early optimizer '
+                             'piece would run before the norm of the whole gradient exists')
+        return float(v)
 
     def _flatten(self):
         n = sum(self.vars[k].numel() for k in self._order)
@@ -312,6 +332,8 @@ class Model(object):
             self._early_hooked = True
 
     def _grad_ready(self, tag, params):
+        if self.grad_clip_norm is not None:
+            return                      # the norm of the whole gradient does not exist yet
         if tag[0] != 'rest' or not self._early_adam or not self._in_step or self._early is not None:
             return
         rng = [self._offs.get(p.data_ptr()) for p in params]
@@ -483,8 +505,19 @@ class Model(object):
             early, early_stream = self._early
             ranges = dist._complement(early, self._flat_grad.numel())
             self._early = None
-        self.ozer.step(self.step_count, self.learn_rate, clip=hparams.GRAD_CLIP_THRES,
-                       grad_scale=grad_scale, zero_grad=not self.keep_grads, ranges=ranges)
+        norm_out = None
+        if self.grad_clip_norm is None:
+            self.ozer.step(self.step_count, self.learn_rate, clip=hparams.GRAD_CLIP_THRES,
+                           grad_scale=grad_scale, zero_grad=not self.keep_grads, ranges=ranges)
+        else:
+            # the gradients alone: the 4 status words in front of the store are no part of the norm.  The partials
+            # are this model's, written and read on this stream every step; (norm, coef) is a NEW tensor every
+            # step, because the caller may keep the returned scalars over many steps (feed.StepReport)
+            self._gclip_partials = ops.grad_sumsq(self._flat_grad, self._gclip_partials)
+            norm_out = torch.empty(2, dtype=torch.float64, device=self.device)
+            self.ozer.step(self.step_count, self.learn_rate, clip=hparams.GRAD_CLIP_THRES,
+                           grad_scale=grad_scale, zero_grad=not self.keep_grads, max_norm=self.grad_clip_norm,
+                           partials=self._gclip_partials, norm_out=norm_out)
         ops.repack_weights(self.device)    # operand-layout copies of the weights the GEMMs read
         if early_stream is not None:
             # joined AFTER the last piece (disjoint ranges): by now the early piece has long
@@ -495,6 +528,9 @@ class Model(object):
         ops.step_done(self.device)
         if self._auto:
             self._auto_tick()
+        if norm_out is not None:
+            return dict(loss=out['loss'].detach(), SNR=out['SNR'], LR=self.learn_rate, grad_norm=norm_out[0],
+                        clip_coef=norm_out[1])
         return dict(loss=out['loss'].detach(), SNR=out['SNR'], LR=self.learn_rate)
 
     def collectives_per_step(self):

@@ -2824,3 +2824,37 @@ def adam_clip_step(theta, grad, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, cl
                                     beta2, eps, clip if clip else 0.0, grad_scale,
                                     int(bool(zero_grad))))
     weights_written(theta)
+
+
+def gclip_partials(n):
+    '''danet_gclip_partials(n): the float64 partials of the sum of squares of n gradient values'''
+    p = _lib.load_gclip().danet_gclip_partials(int(n))
+    if p <= 0:
+        _lib.gclip_check(-1)
+    return p
+
+
+def grad_sumsq(grad, partials=None):
+    '''the sum of squares of the flat fp32 gradient as float64 per-workgroup partials (include/danet_gclip_hip.h);
+    partials: the buffer of a previous call with the same length (None: a new one) -> partials'''
+    n = grad.numel()
+    if partials is None:
+        partials = torch.empty(gclip_partials(n), dtype=torch.float64, device=grad.device)
+    assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous(), partials.dtype
+    _lib.gclip_check(_lib.load_gclip().danet_gclip_sumsq(_lib.stream(), n, ptr(_f32(grad)), ptr(partials),
+                                                         partials.numel()))
+    return partials
+
+
+def adam_gclip_step(theta, grad, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, clip=100.0,
+                    grad_scale=1.0, zero_grad=False, max_norm=None, partials=None, norm_out=None):
+    '''adam_clip_step with the gradient scaled by grad_scale * coef, coef the global-norm clip coefficient formed
+    on the device from `partials` (grad_sumsq of the same gradient) and `max_norm`; norm_out: float64 [2] that
+    receives (norm, coef)'''
+    assert norm_out.is_cuda and norm_out.dtype == torch.float64 and norm_out.numel() == 2
+    assert partials.is_cuda and partials.dtype == torch.float64
+    _lib.gclip_check(_lib.load_gclip().danet_gclip_adam_step(
+        _lib.stream(), theta.numel(), ptr(_f32(theta)), ptr(_f32(grad)), ptr(_f32(m)), ptr(_f32(v)), lr_t, beta1,
+        beta2, eps, clip if clip else 0.0, grad_scale, int(bool(zero_grad)), float(max_norm), ptr(partials),
+        partials.numel(), ptr(norm_out)))
+    weights_written(theta)
