@@ -1,5 +1,5 @@
 '''
-Builds the twelve HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the thirteen HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -16,6 +16,7 @@ Builds the twelve HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_level_hip.so         csrc/level/*.hip         include/danet_level_hip.h
     libdanet_wavloss_hip.so       csrc/wavloss/*.hip       include/danet_wavloss_hip.h
     libdanet_gclip_hip.so         csrc/gclip/*.hip         include/danet_gclip_hip.h
+    libdanet_dpcl_hip.so          csrc/dpcl/*.hip          include/danet_dpcl_hip.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -71,12 +72,14 @@ NOISE = _extension('noise')
 LEVEL = _extension('level')
 WAVLOSS = _extension('wavloss')
 GCLIP = _extension('gclip')
-EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP)
+DPCL = _extension('dpcl')
+EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out
 LEVEL_LIB = LEVEL.out
 WAVLOSS_LIB = WAVLOSS.out
 GCLIP_LIB = GCLIP.out
+DPCL_LIB = DPCL.out
 
 
 def _sources(src_dir):
@@ -188,6 +191,10 @@ def build_wavloss(force=False, verbose=True):
 
 def build_gclip(force=False, verbose=True):
     return _build_spec(GCLIP, force, verbose)
+
+
+def build_dpcl(force=False, verbose=True):
+    return _build_spec(DPCL, force, verbose)
 
 
 def build_variant(name, defs):

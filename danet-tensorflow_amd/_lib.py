@@ -1,6 +1,6 @@
 '''
-ctypes binding of the twelve HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
-libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss and gclip extension libraries.  Each is described
+ctypes binding of the thirteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip and dpcl extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES or EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -222,8 +222,19 @@ GCLIP_PROTOTYPES = {
                                       c_f64, c_p, c_int, c_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_dpcl_hip.h
+DPCL_PROTOTYPES = {
+    'danet_dpcl_abi_version': (c_int, []),
+    'danet_dpcl_last_error': (ctypes.c_char_p, []),
+    'danet_dpcl_chunks': (c_int, [c_i64]),
+    'danet_dpcl_workspace_bytes': (c_sz, [c_int, c_i64, c_int, c_int]),
+    'danet_dpcl_stats': (c_int, [c_p, c_int, c_i64, c_int, c_int, c_p, c_p, c_p, c_sz]),
+    'danet_dpcl_finalize': (c_int, [c_p, c_int, c_i64, c_int, c_int, c_p, c_sz, c_p, c_f32, c_p, c_p, c_p, c_p, c_p]),
+    'danet_dpcl_bwd': (c_int, [c_p, c_int, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_f32, c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Twelve shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Thirteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -293,7 +304,12 @@ WAVLOSS = Library('wavloss', 'libdanet_wavloss_hip.so', 'WAVLOSS_LIB_PATH', '_wa
 GCLIP_ABI_VERSION = 1
 GCLIP = Library('gclip', 'libdanet_gclip_hip.so', 'GCLIP_LIB_PATH', '_gclip', GCLIP_PROTOTYPES,
                 GCLIP_ABI_VERSION, 'danet_gclip_', 'GRAD_CLIP_NORM needs the HIP extension library')
-EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP)
+# loaded at the first train step (or forward pass with the train branch) of a model built with DPCL_WEIGHT set only
+# (ops.dpcl_loss): a run with the key null never maps it
+DPCL_ABI_VERSION = 1
+DPCL = Library('dpcl', 'libdanet_dpcl_hip.so', 'DPCL_LIB_PATH', '_dpcl', DPCL_PROTOTYPES,
+               DPCL_ABI_VERSION, 'danet_dpcl_', 'DPCL_WEIGHT needs the HIP extension library')
+EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -308,7 +324,8 @@ NOISE_LIB_PATH = os.path.join(_CSRC, NOISE.so)
 LEVEL_LIB_PATH = os.path.join(_CSRC, LEVEL.so)
 WAVLOSS_LIB_PATH = os.path.join(_CSRC, WAVLOSS.so)
 GCLIP_LIB_PATH = os.path.join(_CSRC, GCLIP.so)
-_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = _gclip = None
+DPCL_LIB_PATH = os.path.join(_CSRC, DPCL.so)
+_lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = _gclip = _dpcl = None
 _lock = threading.Lock()
 
 
@@ -483,6 +500,17 @@ def load_gclip():
 def gclip_check(rc):
     if rc != 0:
         _check(GCLIP, rc)
+
+
+def load_dpcl():
+    if _dpcl is not None:
+        return _dpcl
+    return _load(DPCL)
+
+
+def dpcl_check(rc):
+    if rc != 0:
+        _check(DPCL, rc)
 
 
 # ---- switches ------------------------------------------------------------------

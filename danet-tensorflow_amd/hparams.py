@@ -38,6 +38,8 @@ unchanged.  Differences, all deliberate:
 * `GRAD_CLIP_NORM` (a finite number > 0, default None = off) makes `Model.train_step` scale the whole gradient so that
   its global L2 norm does not exceed the value (`torch.nn.utils.clip_grad_norm_`'s rule), before the value clip
   `GRAD_CLIP_THRES`; the step then also returns `grad_norm` and `clip_coef`.
+* `DPCL_WEIGHT` (a finite number >= 0, default None = off) adds that many times the deep-clustering affinity loss of
+  the embedding against the ideal binary mask to what `Model.train_step` minimises; the step then also returns `DPCL`.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -115,6 +117,10 @@ DEFAULTS = {
     # the largest global L2 norm of the gradient: beyond it the whole gradient is scaled down to it, ahead of the
     # value clip GRAD_CLIP_THRES; None = off (not in the reference; include/danet_gclip_hip.h)
     'GRAD_CLIP_NORM': None,
+    # the weight of the deep-clustering affinity loss of the embedding (magnitude-ratio weights, ideal-binary-mask
+    # labels) added to the training loss; None = off, 0.0 = computed and reported but without effect (not in the
+    # reference; include/danet_dpcl_hip.h)
+    'DPCL_WEIGHT': None,
 }
 
 

@@ -73,6 +73,8 @@ class Model(object):
         self.train_loss = 'pit-mse'
         self.grad_clip_norm = None
         self._gclip_partials = None
+        # None: off; a float: the weight of the deep-clustering auxiliary loss (build() sets it from DPCL_WEIGHT)
+        self.dpcl_weight = None
 
     # ------------------------------------------------------------ variables
     def get_variable(self, name, shape, init):
@@ -119,6 +121,8 @@ class Model(object):
         # None: off; a float: the largest global L2 norm of the gradient (include/danet_gclip_hip.h)
         self.grad_clip_norm = self._check_grad_clip_norm()
         self._gclip_partials = None
+        # None: off; a float >= 0: the weight of the deep-clustering auxiliary loss (include/danet_dpcl_hip.h)
+        self.dpcl_weight = self._check_dpcl_weight()
         self.encoder = hparams.get_encoder()(self, 'encoder')
         self.estimator = hparams.get_estimator(
             hparams.TRAIN_ESTIMATOR_METHOD)(self, 'train_estimator')
@@ -208,6 +212,22 @@ class Model(object):
         if _lib.expert('early_adam', False):
             raise ValueError('GRAD_CLIP_NORM cannot be combined with the expert setting early_adam: the early optimizer '
                              'piece would run before the norm of the whole gradient exists')
+        return float(v)
+
+    @staticmethod
+    def _check_dpcl_weight():
+        '''DPCL_WEIGHT (null: off) -> None or a float >= 0; ValueError naming the key that rules the value out'''
+        v = getattr(hparams, 'DPCL_WEIGHT', None)
+        if v is None:
+            return None
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError('DPCL_WEIGHT must be null or a number >= 0 (got %r)' % (v,))
+        if not math.isfinite(v) or v < 0:
+            raise ValueError('DPCL_WEIGHT must be null or a finite number >= 0 (got %r)' % (v,))
+        if hparams.EMBED_SIZE > ops.DPCL_MAX_E:
+            raise ValueError('DPCL_WEIGHT needs EMBED_SIZE <= %d (got %d)' % (ops.DPCL_MAX_E, hparams.EMBED_SIZE))
+        if hparams.MAX_N_SIGNAL > ops.DPCL_MAX_C:
+            raise ValueError('DPCL_WEIGHT needs MAX_N_SIGNAL <= %d (got %d)' % (ops.DPCL_MAX_C, hparams.MAX_N_SIGNAL))
         return float(v)
 
     def _flatten(self):
@@ -372,7 +392,9 @@ class Model(object):
         exist only in registers and `sep_pwr` is not in the returned dict.  Needs a separator
         that exposes its activation (`ACT`, the dot-product separators); others take the
         unfused path.  A model built with TRAIN_LOSS = "si-sdr" (`train_loss`) always takes the unfused heads and
-        returns the waveform loss as `loss`, with its own permutation in `loss_perm_idx`.'''
+        returns the waveform loss as `loss`, with its own permutation in `loss_perm_idx`.  A model built with
+        DPCL_WEIGHT set (`dpcl_weight`) returns main loss + weight * deep-clustering loss as `loss` on every head
+        path, and the deep-clustering loss alone as `dpcl`.'''
         B, E = hparams.BATCH_SIZE, hparams.EMBED_SIZE
         eps = float(hparams.EPS)
         if self._noise is None:
@@ -391,6 +413,8 @@ class Model(object):
             s_attractors = self.estimator(                     # main.py:251-254
                 s_embed, s_src_pwr=fe['src_pwr'], s_mix_pwr=fe['mix_pwr'])
             act = getattr(self.separator, 'ACT', None)
+            if self.dpcl_weight is not None:
+                ops.unshare_dembed(s_attractors)       # the embedding gets a third consumer below
             if self.train_loss == 'si-sdr':
                 # the waveform loss needs the separated magnitudes: the unfused heads.  SNR, perm_idx and perms keep
                 # their meaning (one more launch, outside autograd); the loss's own permutation is loss_perm_idx
@@ -412,6 +436,9 @@ class Model(object):
                     s_src_signals, s_sep_pwr, phasor, mode=0, eps=eps)
                 out.update(attrs=s_attractors, sep_pwr=s_sep_pwr, loss=loss, SNR=snr,
                            perm_idx=idx, perms=perms)
+            if self.dpcl_weight is not None:
+                # labels and weights from the CLEAN sources' magnitudes (forward_noisy included)
+                out['loss'], out['dpcl'] = ops.dpcl_loss(s_embed_flat, fe['src_pwr'], out['loss'], self.dpcl_weight)
         if with_valid:
             if self.using_same_method and with_train:
                 s_vattr, s_vsep = out['attrs'], out['sep_pwr']
@@ -458,7 +485,7 @@ class Model(object):
     # ------------------------------------------------------------ train step
     def train_step(self, s_src_signals, sync_metrics=True, s_noise=None, s_noise_gain=None):
         '''one `g_sess.run(train_fetches)` (main.py:430-431): forward, backward,
-        gradient all-reduce, value clip, Adam.  Returns dict(loss, SNR, LR) of
+        gradient all-reduce, value clip, Adam.  Returns dict(loss, SNR, LR[, DPCL][, grad_norm, clip_coef]) of
         device scalars (no host sync unless the caller reads them).  s_noise / s_noise_gain: the step trains on
         the mixture of the sources and that noise against the clean sources (forward_noisy); None: today's step.'''
         # bounded run-ahead + status of the steps that have completed (raises DanetHipError
@@ -528,10 +555,12 @@ class Model(object):
         ops.step_done(self.device)
         if self._auto:
             self._auto_tick()
+        res = dict(loss=out['loss'].detach(), SNR=out['SNR'], LR=self.learn_rate)
+        if self.dpcl_weight is not None:
+            res['DPCL'] = out['dpcl']
         if norm_out is not None:
-            return dict(loss=out['loss'].detach(), SNR=out['SNR'], LR=self.learn_rate, grad_norm=norm_out[0],
-                        clip_coef=norm_out[1])
-        return dict(loss=out['loss'].detach(), SNR=out['SNR'], LR=self.learn_rate)
+            res.update(grad_norm=norm_out[0], clip_coef=norm_out[1])
+        return res
 
     def collectives_per_step(self):
         '''data-path collectives a train step issues under data parallelism (0 without)'''

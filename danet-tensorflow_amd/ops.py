@@ -1029,6 +1029,128 @@ def si_sdr_loss(s_x, s_y_pwr, phasor):
     return SiSdrLossFn.apply(s_x, s_y_pwr, phasor)
 
 
+# ---- deep-clustering auxiliary loss (include/danet_dpcl_hip.h) -----------------------------------------
+# On the extension library libdanet_dpcl_hip.so, mapped at the first call: a run with DPCL_WEIGHT null never gets
+# here.  Forward: dpcl_stats -> dpcl_finalize (which also adds the main loss); backward: ONE launch, dpcl_bwd.
+DPCL_MAX_E = 64                                      # DANET_DPCL_MAX_E
+DPCL_MAX_C = 4                                       # DANET_DPCL_MAX_C
+
+
+def dpcl_workspace_bytes(B, N, E, C):
+    '''danet_dpcl_workspace_bytes(B, N, E, C): the bytes dpcl_stats writes and dpcl_finalize reads'''
+    n = _lib.load_dpcl().danet_dpcl_workspace_bytes(int(B), int(N), int(E), int(C))
+    if n == ctypes.c_size_t(-1).value:
+        _lib.dpcl_check(-1)
+    return n
+
+
+def _dpcl_shapes(embed, src_pwr):
+    assert embed.is_cuda and embed.dtype == torch.float32 and embed.dim() == 3 and embed.is_contiguous(), \
+        (embed.device, embed.dtype, embed.shape)
+    B, N, E = embed.shape
+    assert src_pwr.dtype == torch.float32 and src_pwr.device == embed.device and src_pwr.dim() == 3 \
+        and src_pwr.is_contiguous() and src_pwr.shape[0] == B and src_pwr.shape[2] == N, (src_pwr.dtype, src_pwr.shape)
+    return B, N, E, src_pwr.shape[1]
+
+
+def dpcl_stats(embed, src_pwr, ws=None):
+    '''embed float32 [B, N, E], src_pwr float32 [B, C, N] -> the per-chunk partial sums, a uint8 workspace of
+    dpcl_workspace_bytes(B, N, E, C) bytes (ws: one to write into), ONE launch (danet_dpcl_stats)'''
+    B, N, E, C = _dpcl_shapes(embed, src_pwr)
+    if ws is None:
+        ws = torch.empty(dpcl_workspace_bytes(B, N, E, C), dtype=torch.uint8, device=embed.device)
+    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == embed.device
+    with _lib.timed('dpcl_stats'):
+        _lib.dpcl_check(_lib.load_dpcl().danet_dpcl_stats(_lib.stream(), B, N, E, C, ptr(embed), ptr(src_pwr), ptr(ws),
+                                                          ws.numel()))
+    return ws
+
+
+def dpcl_finalize(ws, B, N, E, C, alpha, main=None, out=None):
+    '''the workspace of dpcl_stats -> (per_utt float64 [B], dpcl float32 [1], total float32 [1] = main + alpha * dpcl,
+    tables float32 [B, E, E + C], cs float32 [B, C + 1]), ONE launch (danet_dpcl_finalize).  main: float32 device
+    scalar or None (= 0); alpha: a host number; out: optional tuple of the five to write into'''
+    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()
+    dev = ws.device
+    if main is not None:
+        assert main.dtype == torch.float32 and main.numel() == 1 and main.device == dev, (main.dtype, main.shape)
+    if out is None:
+        out = (torch.empty(B, dtype=torch.float64, device=dev), torch.empty(1, device=dev), torch.empty(1, device=dev),
+               torch.empty(B, E, E + C, device=dev), torch.empty(B, C + 1, device=dev))
+    per_utt, dpcl, total, tables, cs = out
+    assert per_utt.dtype == torch.float64 and per_utt.numel() == B and per_utt.is_contiguous()
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in (dpcl, total, tables, cs))
+    assert dpcl.numel() == 1 and total.numel() == 1 and tables.numel() == B * E * (E + C) and cs.numel() == B * (C + 1)
+    with _lib.timed('dpcl_finalize'):
+        _lib.dpcl_check(_lib.load_dpcl().danet_dpcl_finalize(
+            _lib.stream(), B, N, E, C, ptr(ws), ws.numel(), ptr(main), float(alpha), ptr(per_utt), ptr(dpcl),
+            ptr(total), ptr(tables), ptr(cs)))
+    return out
+
+
+def dpcl_bwd(embed, src_pwr, tables, cs, scale, dloss=None, out=None):
+    '''the gradient of alpha * dpcl with respect to the embedding, ONE launch (danet_dpcl_bwd): tables, cs as
+    dpcl_finalize wrote them, scale = alpha / B (a host number), dloss float32 device scalar or None (= 1)
+    -> dembed float32 [B, N, E]'''
+    B, N, E, C = _dpcl_shapes(embed, src_pwr)
+    dev = embed.device
+    assert tables.dtype == torch.float32 and tables.is_contiguous() and tuple(tables.shape) == (B, E, E + C) \
+        and tables.device == dev, (tables.dtype, tables.shape)
+    assert cs.dtype == torch.float32 and cs.is_contiguous() and tuple(cs.shape) == (B, C + 1) and cs.device == dev
+    if dloss is not None:
+        assert dloss.dtype == torch.float32 and dloss.numel() == 1 and dloss.device == dev
+    if out is None:
+        out = torch.empty(B, N, E, device=dev)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, N, E) and out.device == dev
+    with _lib.timed('dpcl_bwd'):
+        _lib.dpcl_check(_lib.load_dpcl().danet_dpcl_bwd(_lib.stream(), B, N, E, C, ptr(embed), ptr(src_pwr),
+                                                        ptr(tables), ptr(cs), ptr(dloss), float(scale), ptr(out)))
+    return out
+
+
+class DpclLossFn(torch.autograd.Function):
+    '''main + alpha * (deep-clustering affinity loss of the embedding against the ideal binary mask of src_pwr)
+    (include/danet_dpcl_hip.h): (embed [B,N,E], src_pwr [B,C,N], main scalar, alpha) -> (total, dpcl).  The sum with
+    `main` happens in the finalize kernel; backward is ONE launch and hands `main` the incoming gradient as it is.'''
+
+    @staticmethod
+    def forward(ctx, embed, src_pwr, main, alpha):
+        embed = _f32(embed.contiguous())
+        src_pwr = _f32(src_pwr.contiguous())
+        B, N, E, C = _dpcl_shapes(embed, src_pwr)
+        if _chain():
+            # `main` may still be queued for the side stream (SeparatePitFn's finalize): it has to exist before the
+            # kernel that adds to it, and the tables have to exist before this Function's backward
+            _flush_lazy(embed.device)
+        ws = dpcl_stats(embed, src_pwr)
+        _per_utt, dpcl, total, tables, cs = dpcl_finalize(ws, B, N, E, C, alpha, main=_f32(main))
+        ctx.save_for_backward(embed, src_pwr, tables, cs)
+        ctx.scale = float(alpha) / B
+        total, dpcl = total.view(()), dpcl.view(())
+        ctx.mark_non_differentiable(dpcl)
+        ctx.set_materialize_grads(False)
+        return total, dpcl
+
+    @staticmethod
+    def backward(ctx, dtotal, _ddpcl):
+        if dtotal is None:
+            return None, None, None, None
+        embed, src_pwr, tables, cs = ctx.saved_tensors
+        dembed = None
+        if ctx.needs_input_grad[0]:
+            # dtotal is a device scalar: the kernel reads it (no host sync, no extra pass)
+            dembed = dpcl_bwd(embed, src_pwr, tables, cs, ctx.scale, dloss=_f32(dtotal.contiguous()))
+        return dembed, None, dtotal, None
+
+
+def dpcl_loss(s_embed_flat, s_src_pwr, main, alpha):
+    '''(total, dpcl): total = main + alpha * dpcl as a float32 device scalar, differentiable in the embedding
+    [B, N, E] and in `main`; dpcl = the mean deep-clustering affinity loss, not differentiable.  s_src_pwr [B, C, T, F]
+    or [B, C, N]: the clean sources' magnitudes'''
+    B, N = s_embed_flat.shape[0], s_embed_flat.shape[1]
+    return DpclLossFn.apply(s_embed_flat, s_src_pwr.reshape(B, -1, N), main, alpha)
+
+
 # ---------------------------------------------------------------------------
 # LSTM layer (both directions), raw forward / backward on time-major tensors
 # ---------------------------------------------------------------------------
@@ -2438,10 +2560,11 @@ class _DembedToken(object):
     (`attr._danet_dembed_token`; lost -- and the fusion with it -- if the caller
     transforms the attractors in between), picked up by SeparateFn.forward.  No global
     state, so several models / re-entrant backward passes cannot alias each other.'''
-    __slots__ = ('dembed', 'kind', 'recipe', 'inputs')
+    __slots__ = ('dembed', 'kind', 'recipe', 'inputs', 'share')
 
     def __init__(self):
         self.dembed = None
+        self.share = True         # False: the separator's dembed is NOT handed over (unshare_dembed)
         self.kind = None          # 'anchor': the estimator's backward can recompute the separator's term
         self.recipe = None        # set by SeparatePitFn.backward when it left that term to the estimator
         self.inputs = None        # (embed ptr, numel, mix_pwr ptr or None) the estimator saw
@@ -2463,6 +2586,18 @@ def _new_token(attr):
     tok = _DembedToken()
     attr._danet_dembed_token = tok
     return tok
+
+
+def unshare_dembed(attr):
+    """the embedding behind the attractors `attr` has a consumer besides the estimator and the separator (the
+    deep-clustering loss): the separator's backward must not hand its dembed to the estimator to add into in place.
+    That hand-over relies on the separator's gradient being the tensor autograd keeps for the embedding, which holds
+    only while it is the FIRST gradient to arrive; a consumer created after the heads runs its backward before them.
+    Both modules then return ordinary gradients and autograd adds them.  (The recompute path of the fused heads hands
+    over a recipe, not a buffer, and is not affected.)"""
+    tok = getattr(attr, '_danet_dembed_token', None)
+    if tok is not None:
+        tok.share = False
 
 
 def _take_dembed(tok, numel):
@@ -2654,7 +2789,7 @@ class SeparateFn(torch.autograd.Function):
         check(L.danet_separate_bwd(_lib.stream(), act, B, C, N, E, ptr(mix_pwr), ptr(attr),
                                    ptr(embed_flat), ptr(_f32(dout.contiguous())), ptr(dembed),
                                    ptr(dattr), ptr(w), wn))
-        if ctx.token is not None and ctx.needs_input_grad[1]:
+        if ctx.token is not None and ctx.token.share and ctx.needs_input_grad[1]:
             # the estimator that made `attr` runs its backward next and adds into `dembed`
             ctx.token.dembed = dembed
         return None, dattr, dembed, None, None
@@ -2791,7 +2926,7 @@ class SeparatePitFn(torch.autograd.Function):
             # and returns the whole embedding gradient
             tok.recipe = (act, mode, mix_pwr, src, phasor, records, dl, None)
             return None, dattr, None, None, None, None, None, None
-        if ctx.token is not None and ctx.needs_input_grad[1]:
+        if ctx.token is not None and ctx.token.share and ctx.needs_input_grad[1]:
             # the estimator that made `attr` runs its backward next and adds into `dembed`
             ctx.token.dembed = dembed
         return None, dattr, dembed, None, None, None, None, None
