@@ -1,5 +1,5 @@
 '''
-Builds the thirteen HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the fourteen HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -17,6 +17,7 @@ Builds the thirteen HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_wavloss_hip.so       csrc/wavloss/*.hip       include/danet_wavloss_hip.h
     libdanet_gclip_hip.so         csrc/gclip/*.hip         include/danet_gclip_hip.h
     libdanet_dpcl_hip.so          csrc/dpcl/*.hip          include/danet_dpcl_hip.h
+    libdanet_neval_hip.so         csrc/neval/*.hip         include/danet_neval_hip.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -73,13 +74,15 @@ LEVEL = _extension('level')
 WAVLOSS = _extension('wavloss')
 GCLIP = _extension('gclip')
 DPCL = _extension('dpcl')
-EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL)
+NEVAL = _extension('neval')
+EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL, NEVAL)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out
 LEVEL_LIB = LEVEL.out
 WAVLOSS_LIB = WAVLOSS.out
 GCLIP_LIB = GCLIP.out
 DPCL_LIB = DPCL.out
+NEVAL_LIB = NEVAL.out
 
 
 def _sources(src_dir):
@@ -195,6 +198,10 @@ def build_gclip(force=False, verbose=True):
 
 def build_dpcl(force=False, verbose=True):
     return _build_spec(DPCL, force, verbose)
+
+
+def build_neval(force=False, verbose=True):
+    return _build_spec(NEVAL, force, verbose)
 
 
 def build_variant(name, defs):

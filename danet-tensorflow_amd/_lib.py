@@ -1,6 +1,7 @@
 '''
-ctypes binding of the thirteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
-libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip and dpcl extension libraries.  Each is described
+ctypes binding of the fourteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip, dpcl and neval
+extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES or EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -233,8 +234,18 @@ DPCL_PROTOTYPES = {
     'danet_dpcl_bwd': (c_int, [c_p, c_int, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_f32, c_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_neval_hip.h
+NEVAL_PROTOTYPES = {
+    'danet_neval_abi_version': (c_int, []),
+    'danet_neval_last_error': (ctypes.c_char_p, []),
+    'danet_neval_workspace_bytes': (c_sz, [c_int, c_int, c_int, c_int, c_int]),
+    'danet_neval_synth': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
+    'danet_neval_gram': (c_int, [c_p, c_int, c_int, c_i64, c_p, c_p]),
+    'danet_neval_si_sdr': (c_int, [c_p, c_int, c_int, c_p, c_p, c_p, c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Thirteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Fourteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -309,7 +320,12 @@ GCLIP = Library('gclip', 'libdanet_gclip_hip.so', 'GCLIP_LIB_PATH', '_gclip', GC
 DPCL_ABI_VERSION = 1
 DPCL = Library('dpcl', 'libdanet_dpcl_hip.so', 'DPCL_LIB_PATH', '_dpcl', DPCL_PROTOTYPES,
                DPCL_ABI_VERSION, 'danet_dpcl_', 'DPCL_WEIGHT needs the HIP extension library')
-EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL)
+# loaded at the first valid / test step that is handed a noise component with EVAL_SI_SDR true only
+# (ops.si_sdr_noisy): a run with NOISE_EVAL_DIR or EVAL_SI_SDR null never maps it
+NEVAL_ABI_VERSION = 1
+NEVAL = Library('neval', 'libdanet_neval_hip.so', 'NEVAL_LIB_PATH', '_neval', NEVAL_PROTOTYPES,
+                NEVAL_ABI_VERSION, 'danet_neval_', 'NOISE_EVAL_DIR with EVAL_SI_SDR needs the HIP extension library')
+EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL, NEVAL)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -325,7 +341,9 @@ LEVEL_LIB_PATH = os.path.join(_CSRC, LEVEL.so)
 WAVLOSS_LIB_PATH = os.path.join(_CSRC, WAVLOSS.so)
 GCLIP_LIB_PATH = os.path.join(_CSRC, GCLIP.so)
 DPCL_LIB_PATH = os.path.join(_CSRC, DPCL.so)
+NEVAL_LIB_PATH = os.path.join(_CSRC, NEVAL.so)
 _lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = _gclip = _dpcl = None
+_neval = None
 _lock = threading.Lock()
 
 
@@ -511,6 +529,17 @@ def load_dpcl():
 def dpcl_check(rc):
     if rc != 0:
         _check(DPCL, rc)
+
+
+def load_neval():
+    if _neval is not None:
+        return _neval
+    return _load(NEVAL)
+
+
+def neval_check(rc):
+    if rc != 0:
+        _check(NEVAL, rc)
 
 
 # ---- switches ------------------------------------------------------------------

@@ -144,14 +144,18 @@ def restore_checkpoint(model, filename):
 
 def evaluate(model, dataset, subset, out=sys.stdout, sync_feed=None):
     '''validation / test sweep with valid_fetches (main.py:486-510, :512-532); fed like
-    train_epoch (no crop: main.py:497-498)'''
+    train_epoch (no crop: main.py:497-498).  A feed.NoisyBatch (the wavdir dataset with NOISE_EVAL_DIR set) is
+    unpacked into valid_step's three arguments, as train_epoch does for train_step.'''
     if sync_feed is None:
         sync_feed = SYNC_FEED
     src = feed.open_feed(feed.EpochSource(dataset, subset, hparams.BATCH_SIZE * hparams.MAX_N_SIGNAL,
                                           shuffle=False), model.device, None, sync_feed)
     report = feed.StepReport(flush_every=1 if sync_feed else 1024)
     for spectra in src:
-        report.add(model.valid_step(spectra))
+        if isinstance(spectra, feed.NoisyBatch):
+            report.add(model.valid_step(spectra.src, s_noise=spectra.noise, s_noise_gain=spectra.gain))
+        else:
+            report.add(model.valid_step(spectra))
         model.reset_state()
         out.write('.')
         out.flush()
@@ -166,7 +170,8 @@ def _draw_aligned_sources(dataset, shuffle=False):
     '''one data point of hparams.MAX_N_SIGNAL single-speaker spectra from the test subset,
     each zero-padded at a random position of the time axis (utils.random_zeropad) to the
     longest of them rounded up to a multiple of hparams.LENGTH_ALIGN -- main.py:662-672
-    (demo) and :719-727 (debug).  Returns complex [C, T, F].'''
+    (demo) and :719-727 (debug).  Returns complex [C, T, F].  Reads element 0 of the data point and ignores the noise
+    a wavdir dataset with NOISE_EVAL_DIR set yields as element 1: demo and debug stay clean.'''
     src_signals = []
     for src_signals in dataset.epoch('test', hparams.MAX_N_SIGNAL, shuffle=shuffle):
         break

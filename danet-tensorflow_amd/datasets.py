@@ -210,8 +210,8 @@ class WavDirData(Dataset):
 
     ADDITIVE NOISE (hparams.NOISE_DIR = a folder of noise recordings, NOISE_SNR_MIN = lo, NOISE_SNR_MAX = hi, dB,
     -30 <= lo <= hi <= 60; all three default None = off: no launch, no allocation, no draw, libdanet_noise_hip.so not
-    mapped).  `train` only; `valid` / `test` batches are those without the keys, bit for bit (EVAL_SI_SDR derives its
-    mixture baseline from the clean references by linearity).  NOISE_DIR/**/*.wav is discovered and decoded like the
+    mapped).  `train` only; `valid` / `test` batches are those without the keys, bit for bit (their noise has keys of
+    its own: NOISY EVALUATION below).  NOISE_DIR/**/*.wav is discovered and decoded like the
     dataset's own files into ONE more pool (files shorter than FFT_SIZE skipped and counted).  After a train batch
     is planned as without the keys, plan_noise (the rule include/danet_noise_hip.h writes out) draws per MIXTURE a
     noise file, a position and an SNR from a fifth RandomState, seeded by (dist.shard_seed(1337), subset index, 3):
@@ -225,9 +225,23 @@ class WavDirData(Dataset):
     (spectra, noise) with the noise already scaled (ops.mix_scale_: the same single rounding), so both routes give
     the same mixture bit for bit.
 
+    NOISY EVALUATION (hparams.NOISE_EVAL_DIR = a folder of held-out noise recordings, NOISE_EVAL_SNR_MIN = lo,
+    NOISE_EVAL_SNR_MAX = hi, dB, -30 <= lo <= hi <= 60; all three default None = off: `valid` / `test` are what they
+    are without the keys, bit for bit, no launch, no allocation, no draw).  Independent of the three train keys: either
+    family works without the other and the two folders may be the same path.  A second pool with its own file,
+    offset, length and power tables, read by load_host only when the key is set, uploaded and measured
+    (ops.mix_power) at the first noisy evaluation batch.  A `valid` / `test` batch is planned as without the keys;
+    then plan_noise, unchanged, runs on the eval tables and bounds with a stream seeded (dist.shard_seed(1337), subset
+    index, 4) that is created anew at the start of every sweep (noise_eval_stream): every evaluation sees the same
+    noisy mixtures.  `train` never uses this stream or this pool, and `random`, `np.random` and the mix / speed /
+    reverb / train-noise streams advance exactly as without the keys.  Both routes carry the noise as for `train`:
+    epoch() yields (spectra, noise) with the noise already scaled, epoch_device() yields feed.NoisyBatch(src, noise,
+    gains) from one more ops.stft_batch launch into the noise ring, and cli.evaluate hands the three to
+    Model.valid_step (include/danet_neval_hip.h: the metric whose baseline is that noisy mixture).
+
     ACTIVE SPEECH LEVEL (hparams.MIX_LEVEL_MEASURE = "active", default None = mean power: no launch, no allocation,
-    libdanet_level_hip.so not mapped, every batch bit for bit what it is without the key).  Needs MIX_SNR_RANGE or
-    NOISE_DIR: MIX_LEVEL_RANGE alone uses no power.  `train`, `valid` and `test` alike: when a subset's power table
+    libdanet_level_hip.so not mapped, every batch bit for bit what it is without the key).  Needs MIX_SNR_RANGE,
+    NOISE_DIR or NOISE_EVAL_DIR: MIX_LEVEL_RANGE alone uses no power.  `train`, `valid` and `test` alike: when a subset's power table
     is measured -- once per pool, an aliased `valid` sharing `test`'s -- ops.mix_power is followed by ONE pass of
     ops.level_activity over the same pool (in launches of rows of similar length whose workspace stays under
     LEVEL_WS_BYTES: level_chunks), and the table holds every file's ITU-T P.56 active power A_c (the rule
@@ -257,6 +271,11 @@ class WavDirData(Dataset):
         self.noise_files, self.noise_lengths, self.noise_offsets = [], None, None
         self.noise_pool_host, self.noise_skipped, self.noise_power = None, 0, None
         self._noise_rng, self._noise_pool_dev = {}, {}
+        # the held-out pool of `valid` / `test` (NOISE_EVAL_*): the same tables a second time
+        self.noise_eval_dir = self.noise_eval_snr = None
+        self.noise_eval_files, self.noise_eval_lengths, self.noise_eval_offsets = [], None, None
+        self.noise_eval_pool_host, self.noise_eval_skipped, self.noise_eval_power = None, 0, None
+        self._noise_eval_pool_dev = {}
         self.level_key = None       # read from hparams by load_host: None (mean power) or 'active'
         self._alias = False
 
@@ -337,12 +356,17 @@ class WavDirData(Dataset):
         ValueError that names the offending key: a folder that is not a string, a folder without both bounds (the
         missing bound is named), a bound without the folder (NOISE_DIR is named), a bound that is a bool, not a
         number, outside [-30, 60] dB, or lo > hi'''
-        folder = getattr(hparams, 'NOISE_DIR', None)
-        keys = ('NOISE_SNR_MIN', 'NOISE_SNR_MAX')
+        return WavDirData._noise_family('NOISE')
+
+    @staticmethod
+    def _noise_family(family):
+        '''the rule of noise_keys for the keys <family>_DIR, <family>_SNR_MIN, <family>_SNR_MAX'''
+        dkey, keys = family + '_DIR', (family + '_SNR_MIN', family + '_SNR_MAX')
+        folder = getattr(hparams, dkey, None)
         raw = [getattr(hparams, k, None) for k in keys]
         if folder is not None and not isinstance(folder, str):
-            raise ValueError('hparams.NOISE_DIR must be null or the path of a folder of noise recordings, got %r'
-                             % (folder,))
+            raise ValueError('hparams.%s must be null or the path of a folder of noise recordings, got %r'
+                             % (dkey, folder))
         lo_lim, hi_lim = WavDirData.NOISE_SNR_LIMITS
         vals = []
         for key, v in zip(keys, raw):
@@ -352,23 +376,37 @@ class WavDirData(Dataset):
                                      % (key, lo_lim, hi_lim, v))
                 v = float(v)
             vals.append(v)
+        together = 'additive noise needs %s, %s and %s together' % ((dkey,) + keys)
         if folder is None:
             for key, v in zip(keys, vals):
                 if v is not None:
-                    raise ValueError('hparams.%s is set but hparams.NOISE_DIR is null: additive noise needs NOISE_DIR, '
-                                     'NOISE_SNR_MIN and NOISE_SNR_MAX together' % key)
+                    raise ValueError('hparams.%s is set but hparams.%s is null: %s' % (key, dkey, together))
             return None, None
         for key, v in zip(keys, vals):
             if v is None:
-                raise ValueError('hparams.NOISE_DIR is set but hparams.%s is null: additive noise needs NOISE_DIR, '
-                                 'NOISE_SNR_MIN and NOISE_SNR_MAX together' % key)
+                raise ValueError('hparams.%s is set but hparams.%s is null: %s' % (dkey, key, together))
         if vals[0] > vals[1]:
-            raise ValueError('hparams.NOISE_SNR_MIN = %r is above hparams.NOISE_SNR_MAX = %r' % (vals[0], vals[1]))
+            raise ValueError('hparams.%s = %r is above hparams.%s = %r' % (keys[0], vals[0], keys[1], vals[1]))
         return folder, (vals[0], vals[1])
+
+    @staticmethod
+    def noise_eval_keys():
+        '''(NOISE_EVAL_DIR, (NOISE_EVAL_SNR_MIN, NOISE_EVAL_SNR_MAX)) or (None, None): noise_keys for the held-out
+        family, independent of the train family'''
+        return WavDirData._noise_family('NOISE_EVAL')
 
     @property
     def noise_on(self):
         return self.noise_dir is not None
+
+    @property
+    def noise_eval_on(self):
+        return self.noise_eval_dir is not None
+
+    def noisy(self, subset):
+        '''does a batch of `subset` carry a noise component: `train` with NOISE_DIR, `valid` / `test` with
+        NOISE_EVAL_DIR'''
+        return self.noise_on if subset == 'train' else self.noise_eval_on
 
     LEVEL_MARGIN_DB = 15.9            # P.56: the active level sits this far above the threshold that defines it
     LEVEL_WS_BYTES = 64 << 20         # workspace of one ops.level_activity launch of power_table
@@ -433,6 +471,29 @@ class WavDirData(Dataset):
             out[u] = 10.0 ** (level / 10.0)
         return out
 
+    def load_noise_eval_host(self, out=None):
+        '''discover, decode and resample NOISE_EVAL_DIR into ONE host pool of its own, exactly as load_noise_host
+        does NOISE_DIR (the two folders may be the same path: two pools all the same)'''
+        folder = self.noise_eval_dir
+        if not os.path.isdir(folder):
+            raise IOError('wavdir: NOISE_EVAL_DIR folder %s not found' % folder)
+        files, waves, skipped = [], [], 0
+        for fn in self.discover(folder):
+            w = self.read_wave(fn)
+            if len(w) < hparams.FFT_SIZE:
+                skipped += 1
+                continue
+            files.append(fn)
+            waves.append(w)
+        print('wavdir held-out evaluation noise (NOISE_EVAL_DIR): %d files, %d shorter than FFT_SIZE skipped'
+              % (len(files), skipped), file=out)
+        if not files:
+            raise IOError('wavdir: no usable WAV file under NOISE_EVAL_DIR = %s' % folder)
+        lens = np.asarray([len(w) for w in waves], dtype=np.int64)
+        self.noise_eval_files, self.noise_eval_lengths, self.noise_eval_skipped = files, lens, skipped
+        self.noise_eval_offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        self.noise_eval_pool_host = np.concatenate(waves)
+
     def load_noise_host(self, out=None):
         '''discover, decode and resample NOISE_DIR into ONE host pool, exactly like a subset's own files'''
         folder = self.noise_dir
@@ -460,8 +521,10 @@ class WavDirData(Dataset):
         self.speed_range = self.speed_perturb_range()
         self.reverb_rt60 = self.reverb_rt60_max()
         self.noise_dir, self.noise_snr = self.noise_keys()
+        self.noise_eval_dir, self.noise_eval_snr = self.noise_eval_keys()
         self.level_key = self.level_measure()
-        if self.level_key is not None and self.mix_snr_range is None and self.noise_dir is None:
+        if (self.level_key is not None and self.mix_snr_range is None and self.noise_dir is None
+                and self.noise_eval_dir is None):       # (the eval noise rule uses source powers as the train rule)
             raise ValueError('hparams.MIX_LEVEL_MEASURE = %r would do nothing: no source power is used with both '
                              'MIX_SNR_RANGE and NOISE_DIR null (MIX_LEVEL_RANGE alone shifts a mixture without '
                              'measuring it); set one of the two or leave the key null' % (self.level_key,))
@@ -499,6 +562,8 @@ class WavDirData(Dataset):
                 table['valid'] = table['test']
         if self.noise_on:
             self.load_noise_host(out)
+        if self.noise_eval_on:
+            self.load_noise_eval_host(out)
 
     def install_and_load(self):
         self.load_host()
@@ -658,6 +723,22 @@ class WavDirData(Dataset):
                 [dist.shard_seed(1337), self.SUBSETS.index(subset), 3])
         return self._noise_rng[subset]
 
+    def noise_eval_stream(self, subset):
+        '''the RandomState the noise of a `valid` / `test` sweep is drawn from, seeded by (dist.shard_seed(1337),
+        subset index, 4) and created ANEW by every call -- the start of a sweep, as mix_stream treats these subsets:
+        every evaluation sees the same noisy mixtures, ranks draw differently, and `valid` aliased to `test` still has
+        its own subset index.  None with the keys null and for `train`, which never uses this stream or this pool'''
+        if not self.noise_eval_on or subset == 'train':
+            return None
+        from . import dist
+        return np.random.RandomState([dist.shard_seed(1337), self.SUBSETS.index(subset), 4])
+
+    def noise_tables(self, subset):
+        '''(offsets, lengths, powers, (lo, hi)) of the pool `subset` draws its noise from'''
+        if subset == 'train':
+            return self.noise_offsets, self.noise_lengths, self.noise_power, self.noise_snr
+        return self.noise_eval_offsets, self.noise_eval_lengths, self.noise_eval_power, self.noise_eval_snr
+
     def _pool_key(self, subset):
         return 'test' if (subset == 'valid' and self._alias) else subset
 
@@ -710,20 +791,24 @@ class WavDirData(Dataset):
             yield idx, T_max, pads, beg, cnt, gains, speed, rows
 
     def plan_epoch_noise(self, subset, batch_size, shuffle=False, crop_len=None, crop=False):
-        '''plan_epoch_reverb with a ninth field: None, or -- `train` with NOISE_DIR set -- the NoisePlan of
-        plan_noise, drawn per batch AFTER everything else from a stream of its own (nothing else moves).  Needs the
-        power tables (self.power, self.noise_power: the device half measures them)'''
-        noise_rng = self.noise_stream(subset)
+        '''plan_epoch_reverb with a ninth field: None, or -- `train` with NOISE_DIR set, `valid` / `test` with
+        NOISE_EVAL_DIR set -- the NoisePlan of plan_noise on that subset's pool and bounds (noise_tables), drawn per
+        batch AFTER everything else from a stream of its own (nothing else moves).  Needs the power tables
+        (self.power, self.noise_power / self.noise_eval_power: the device half measures them)'''
+        noise_rng = self.noise_stream(subset) if subset == 'train' else self.noise_eval_stream(subset)
         C = hparams.MAX_N_SIGNAL
         if noise_rng is not None and batch_size % C:
-            raise ValueError('wavdir: with NOISE_DIR set the batch size must be a multiple of MAX_N_SIGNAL = %d (got '
-                             '%d): noise is drawn per mixture' % (C, batch_size))
+            raise ValueError('wavdir: with %s set the batch size must be a multiple of MAX_N_SIGNAL = %d (got '
+                             '%d): noise is drawn per mixture'
+                             % ('NOISE_DIR' if subset == 'train' else 'NOISE_EVAL_DIR', C, batch_size))
+        if noise_rng is not None:
+            offsets, lengths, powers, (lo, hi) = self.noise_tables(subset)
         for item in self.plan_epoch_reverb(subset, batch_size, shuffle, crop_len, crop):
             noise = None
             if noise_rng is not None:
                 noise = self.plan_noise(self.power[self._pool_key(subset)][item[0]], item[5], noise_rng, C,
-                                        self.noise_offsets, self.noise_lengths, self.noise_power, item[1],
-                                        self.noise_snr[0], self.noise_snr[1], hparams.FFT_SIZE, hparams.FFT_STRIDE)
+                                        offsets, lengths, powers, item[1], lo, hi, hparams.FFT_SIZE,
+                                        hparams.FFT_STRIDE)
             yield item + (noise,)
 
     # ---- device half -----------------------------------------------------------------------------
@@ -786,6 +871,22 @@ class WavDirData(Dataset):
             step = max(1, int(ws_bytes) // (tiles * (16 + 12 * ops.LEVEL_THRESHOLDS)))
             yield order[a:a + step]
             a += step
+
+    def upload_noise_eval(self, device):
+        '''upload_noise for the held-out pool of NOISE_EVAL_DIR: uploaded once, and measured once (ops.mix_power), at
+        the first noisy evaluation batch'''
+        import torch
+        pool = self._noise_eval_pool_dev.get(str(device))
+        if pool is None:
+            pool = self._noise_eval_pool_dev[str(device)] = torch.from_numpy(self.noise_eval_pool_host).to(device)
+        if self.noise_eval_power is None:
+            from . import ops
+            sums = ops.mix_power(pool, self.noise_eval_offsets, self.noise_eval_lengths).cpu().numpy()
+            self.noise_eval_power = sums / self.noise_eval_lengths.astype(np.float64)
+        return pool
+
+    def _noise_pool_on(self, device, subset):
+        return self.upload_noise(device) if subset == 'train' else self.upload_noise_eval(device)
 
     def upload_noise(self, device):
         '''the float32 noise pool on `device` (uploaded once) and, measured on it once, every noise file's float64
@@ -875,10 +976,10 @@ class WavDirData(Dataset):
         from . import ops
         device = self._device(device)
         pool, window = self.upload_pool(subset, device), self._window_on(device)
-        noisy = self.noise_on and subset == 'train'
+        noisy = self.noisy(subset)
         if self.mix_on or noisy:
             self.power_table(subset, pool)
-        noise_pool = self.upload_noise(device) if noisy else None
+        noise_pool = self._noise_pool_on(device, subset) if noisy else None
         for idx, T_max, pads, _beg, _cnt, gains, speed, rows, noise in self.plan_epoch_noise(subset, batch_size,
                                                                                              shuffle):
             src, offsets, lengths = pool, self.offsets[subset][idx], self.lengths[subset][idx]
@@ -918,7 +1019,7 @@ class WavDirData(Dataset):
             row += ops.SPEED_DESC_DTYPE.itemsize                            # + one speed descriptor
         if self.reverb_rt60 is not None:
             row += ops.REVERB_DESC_DTYPE.itemsize                           # + one reverb descriptor
-        if self.noise_on:
+        if self.noise_on or self.noise_eval_on:
             row += ops.PREP_DESC_DTYPE.itemsize + 4 + 8     # per MIXTURE a noise descriptor and a gain (+ alignment)
         ring = self._ring.get(str(device))
         if ring is None or ring['n_utt'] < n_utt or ring['row'] < row:
@@ -941,8 +1042,8 @@ class WavDirData(Dataset):
         without a host wait.  Everything is enqueued on the
         stream that is current in the consumer.  LIFETIME: a yielded tensor is a view of one of
         OUT_DEPTH reused device buffers and stays valid until the consumer has asked for OUT_DEPTH - 1
-        more batches (the same rule as feed.BatchFeed; clone it to keep it longer).  `train` with NOISE_DIR set: one
-        more launch per batch, and what is yielded is a feed.NoisyBatch(src, noise [B, T', F], gains [B]) whose
+        more batches (the same rule as feed.BatchFeed; clone it to keep it longer).  `train` with NOISE_DIR set, and
+        `valid` / `test` with NOISE_EVAL_DIR set: one more launch per batch, and what is yielded is a feed.NoisyBatch(src, noise [B, T', F], gains [B]) whose
         three tensors live by the same rule.'''
         if not self.is_loaded:
             raise RuntimeError('Dataset is not loaded.')
@@ -950,11 +1051,11 @@ class WavDirData(Dataset):
         F, B, C = hparams.FEATURE_SIZE, hparams.BATCH_SIZE, hparams.MAX_N_SIGNAL
         assert batch_size == B * C, (batch_size, B, C)
         pool, window = self.upload_pool(subset, device), self._window_on(device)
-        noisy = self.noise_on and subset == 'train'
+        noisy = self.noisy(subset)
         if self.mix_on or noisy:
             self.power_table(subset, pool)
         if noisy:
-            self.upload_noise(device)
+            self._noise_pool_on(device, subset)
         ring = self._take_ring(device, batch_size)
         for idx, T_max, pads, beg, cnt, gains, speed, rows, noise in self.plan_epoch_noise(subset, batch_size, shuffle,
                                                                                            crop_len, crop=True):
@@ -1016,7 +1117,7 @@ class WavDirData(Dataset):
             slot.pin[at:sent].numpy().view(np.float32)[:] = gains
             dev_gains = slot.dev[at:sent].view(torch.float32)
         if noise is not None:             # 24-byte rows (8-byte aligned) and float32 [mixtures] behind everything
-            noise_pool, n_mix = self.upload_noise(device), len(noise.gains)
+            noise_pool, n_mix = self._noise_pool_on(device, subset), len(noise.gains)
             at = (sent + 7) & ~7
             sent = at + n_mix * row
             ops.prep_desc(noise.offsets, noise.lengths, noise.pads, T_max, noise_pool.numel(), N, S,

@@ -37,8 +37,9 @@ from .hparams import hparams
 
 
 # what a feed yields instead of a tensor when the mixture has a component that is not a target (the wavdir dataset
-# with NOISE_DIR set): src complex64 [B, C, T', F], noise complex64 [B, T', F], gain float32 [B] or None (the noise
-# is already scaled); cli.train_epoch unpacks it into Model.train_step(src, s_noise=noise, s_noise_gain=gain)
+# with NOISE_DIR set, or -- `valid` / `test` -- NOISE_EVAL_DIR): src complex64 [B, C, T', F], noise complex64 [B, T', F],
+# gain float32 [B] or None (the noise is already scaled); cli.train_epoch unpacks it into Model.train_step(src,
+# s_noise=noise, s_noise_gain=gain), cli.evaluate into Model.valid_step in the same way
 NoisyBatch = collections.namedtuple('NoisyBatch', 'src noise gain')
 
 

@@ -28,6 +28,10 @@ unchanged.  Differences, all deliberate:
 * `NOISE_DIR` (a folder of noise recordings) with `NOISE_SNR_MIN` / `NOISE_SNR_MAX` (dB, -30 <= min <= max <= 60;
   all three default None = off) make the `wavdir` dataset add a drawn segment of a drawn noise file to every train
   mixture at a drawn SNR, the targets staying clean; every other dataset ignores them.
+* `NOISE_EVAL_DIR` (a folder of held-out noise recordings) with `NOISE_EVAL_SNR_MIN` / `NOISE_EVAL_SNR_MAX` (dB,
+  -30 <= min <= max <= 60; all three default None = off) do the same to every `valid` / `test` mixture of the `wavdir`
+  dataset, the same noise in every sweep; independent of the `NOISE_*` keys; with `EVAL_SI_SDR` true `Model.valid_step`
+  then reports `SI-SDR` / `SI-SDRi` against the noisy mixture and `nSNR`; every other dataset ignores them.
 * `MIX_LEVEL_MEASURE` (`"active"`, default None = mean power over the whole file) makes the `wavdir` dataset set
   `MIX_SNR_RANGE` / `NOISE_SNR_*` levels from every source's ITU-T P.56 active speech level, pauses excluded;
   every other dataset ignores it.
@@ -108,6 +112,12 @@ DEFAULTS = {
     'NOISE_DIR': None,
     'NOISE_SNR_MIN': None,
     'NOISE_SNR_MAX': None,
+    # additive noise in the `wavdir` dataset's valid / test subsets: a folder of held-out noise recordings
+    # (NOISE_EVAL_DIR/**/*.wav) and the range the SNR of every mixture is drawn from, dB in [-30, 60]; all three
+    # None = off; independent of the three train keys above (not in the reference; include/danet_neval_hip.h)
+    'NOISE_EVAL_DIR': None,
+    'NOISE_EVAL_SNR_MIN': None,
+    'NOISE_EVAL_SNR_MAX': None,
     # what a source's level is in the `wavdir` dataset's MIX_SNR_RANGE / NOISE_SNR_* rules: None = its mean power over
     # the whole file, "active" = its ITU-T P.56 active speech level (not in the reference; include/danet_level_hip.h)
     'MIX_LEVEL_MEASURE': None,

@@ -569,9 +569,23 @@ class Model(object):
         return {'0': 1, 'tail': 2}.get(self.grad_schedule,
                                        1 + hparams.NUM_LSTM_LAYERS + 1)   # '1': per-layer buckets
 
-    def valid_step(self, s_src_signals):
-        '''`g_sess.run(valid_fetches)` (main.py:499-500)'''
+    def valid_step(self, s_src_signals, s_noise=None, s_noise_gain=None):
+        '''`g_sess.run(valid_fetches)` (main.py:499-500).  s_noise / s_noise_gain (the wavdir dataset's
+        NOISE_EVAL_DIR): the step evaluates the mixture of the sources and that noise against the clean sources
+        (forward_noisy) -- `loss` and `SNR` are the reference's validation loss of the noisy mixture, and with
+        EVAL_SI_SDR true `SI-SDR`, `SI-SDRi` (against the noisy mixture the model was given) and `nSNR` (sources to
+        noise, dB) come from ops.si_sdr_noisy; None: today's step.'''
         ops.poll_status(self.device)
+        if s_noise is not None:
+            with torch.no_grad():
+                out = self.forward_noisy(s_src_signals, s_noise, s_noise_gain, with_valid=True, with_train=False)
+                res = dict(loss=out['valid_loss'], SNR=out['valid_SNR'])
+                if self.eval_si_sdr:
+                    est = ops.reattach_phase(out['sep_pwr_valid'], out['phasor'])
+                    res['SI-SDR'], res['SI-SDRi'], res['nSNR'] = ops.si_sdr_noisy(
+                        s_src_signals, est, s_noise, s_noise_gain)[:3]
+            ops.step_done(self.device, collective_consistent=not dist.is_dist())
+            return res
         with torch.no_grad():
             out = self.forward(s_src_signals, with_valid=True, with_train=False)
             res = dict(loss=out['valid_loss'], SNR=out['valid_SNR'])

@@ -926,6 +926,117 @@ def si_sdr(src, est, fft_stride=None):
     return mean2[0], mean2[1], per_utt, perm_idx
 
 
+# ---- waveform metric of a noisy valid / test sweep (include/danet_neval_hip.h) -------------------------
+# On the extension library libdanet_neval_hip.so, mapped at the first call: a run with NOISE_EVAL_DIR or EVAL_SI_SDR
+# null never gets here.  Three launches: spectra (+ the scaled noise) -> waveforms -> Gram matrices -> decibels; the
+# baseline of SI-SDRi is the mixture the model was given, sources + noise.
+NEVAL_MAX_C = 4                                      # DANET_NEVAL_MAX_C
+_neval_ws = {}           # (device index, stream, B, C, T, N, S) -> (scratch, wav, G, per_utt, mean3, perm_idx)
+
+
+def _neval_workspace(B, C, T, N, S, dev):
+    '''(buffer, wav, G, per_utt, mean3, perm_idx): the views one shape cuts out of the grow-only scratch of this
+    (device, stream), in the layout of danet_neval_workspace_bytes; cached per shape'''
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
+           torch.cuda.current_stream().cuda_stream, B, C, T, N, S)
+    hit = _neval_ws.get(key)
+    if hit is not None and _lib._ws.get(key[:2] + ('neval',)) is hit[0]:
+        return hit
+    nbytes = _lib.load_neval().danet_neval_workspace_bytes(B, C, T, N, S)
+    if nbytes == ctypes.c_size_t(-1).value:
+        _lib.neval_check(-1)
+    buf = _lib.workspace(nbytes, dev, 'neval')
+    M, Ls = 2 * C + 1, (T - 1) * S
+    views, off = [], 0
+    for shape, dtype, size in (((B, M, Ls), torch.float32, 4), ((B, M, M), torch.float64, 8),
+                               ((B, 3), torch.float64, 8), ((3,), torch.float64, 8), ((B,), torch.int32, 4)):
+        n = int(np.prod(shape)) * size
+        views.append(buf[off:off + n].view(dtype).view(shape))
+        off += (n + 255) & ~255
+    assert off == nbytes, (off, nbytes)
+    if len(_neval_ws) >= 64:
+        _neval_ws.clear()
+    hit = _neval_ws[key] = (buf,) + tuple(views)
+    return hit
+
+
+def neval_synth(src, est, noise, gain, fft_stride, window=None, out=None):
+    '''references and UNPERMUTED estimates, complex64 [B, C, T, F], noise complex64 [B, T, F], gain float32 [B] or
+    None (= 1) -> float32 waveforms [B, 2C + 1, (T - 1) * S]: references, estimates, then the synthesis of
+    fl(gain * noise), ONE launch (danet_neval_synth).  window: float32 device vector [N] (default hparams.FFT_WND).'''
+    assert src.is_cuda and src.dtype == torch.complex64 and src.dim() == 4, (src.dtype, src.shape)
+    assert est.is_cuda and est.dtype == torch.complex64 and est.shape == src.shape and est.device == src.device
+    B, C, T, F = src.shape
+    assert noise.dtype == torch.complex64 and noise.device == src.device and tuple(noise.shape) == (B, T, F), \
+        (noise.device, noise.dtype, noise.shape)
+    if gain is not None:
+        assert gain.dtype == torch.float32 and gain.device == src.device and tuple(gain.shape) == (B,) \
+            and gain.is_contiguous(), (gain.device, gain.dtype, gain.shape)
+    src, est, noise = src.contiguous(), est.contiguous(), noise.contiguous()
+    N = 2 * (F - 1)
+    window = _metric_window(src.device) if window is None else _f32(window).contiguous()
+    assert window.numel() == N and window.device == src.device, (window.numel(), N)
+    if out is None:
+        out = torch.empty(B, 2 * C + 1, max(T - 1, 0) * fft_stride, dtype=torch.float32, device=src.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() \
+        and tuple(out.shape) == (B, 2 * C + 1, (T - 1) * fft_stride)
+    with _lib.timed('neval_synth'):
+        _lib.neval_check(_lib.load_neval().danet_neval_synth(
+            _lib.stream(), B, C, T, N, fft_stride, ptr(torch.view_as_real(src)), ptr(torch.view_as_real(est)),
+            ptr(torch.view_as_real(noise)), ptr(gain), ptr(window), ptr(out)))
+    return out
+
+
+def neval_gram(wav, out=None):
+    '''float32 [B, M, Ls], M <= 9 -> float64 Gram matrices [B, M, M], ONE launch (danet_neval_gram: the tree of
+    danet_metric_gram; symmetric bit for bit)'''
+    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.is_contiguous()
+    B, M, Ls = wav.shape
+    if out is None:
+        out = torch.empty(B, M, M, dtype=torch.float64, device=wav.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B, M, M)
+    with _lib.timed('neval_gram'):
+        _lib.neval_check(_lib.load_neval().danet_neval_gram(_lib.stream(), B, M, Ls, ptr(wav), ptr(out)))
+    return out
+
+
+def neval_finalize(G, out=None):
+    '''float64 Gram matrices [B, 2C + 1, 2C + 1] -> (mean3 [3], per_utt [B, 3], perm_idx int32 [B]): SI-SDR, SI-SDRi
+    against the noisy mixture, nSNR; ONE launch (danet_neval_si_sdr); out: optional (per_utt, perm_idx, mean3)'''
+    assert G.is_cuda and G.dtype == torch.float64 and G.dim() == 3 and G.is_contiguous() and G.shape[1] == G.shape[2]
+    B, M = G.shape[0], G.shape[1]
+    assert M % 2 == 1, M
+    if out is None:
+        out = (torch.empty(B, 3, dtype=torch.float64, device=G.device),
+               torch.empty(B, dtype=torch.int32, device=G.device), torch.empty(3, dtype=torch.float64, device=G.device))
+    per_utt, perm_idx, mean3 = out
+    with _lib.timed('neval_si_sdr'):
+        _lib.neval_check(_lib.load_neval().danet_neval_si_sdr(_lib.stream(), B, (M - 1) // 2, ptr(G), ptr(per_utt),
+                                                              ptr(perm_idx), ptr(mean3)))
+    return mean3, per_utt, perm_idx
+
+
+def si_sdr_noisy(src, est, noise, gain=None, fft_stride=None):
+    '''SI-SDR, SI-SDRi and nSNR (dB) of the waveforms of the UNPERMUTED estimates `est` against the clean references
+    `src`, both complex64 [B, C, T, F], for a mixture that held fl(gain * noise) as well (noise complex64 [B, T, F],
+    gain float32 [B] or None = 1): the baseline of SI-SDRi is that noisy mixture, nSNR the ratio of the summed
+    sources to the noise -> (si_sdr, si_sdri, nsnr, per_utt [B, 3], perm_idx [B]): float64 / int32 device tensors
+    of the caller's own (allocated here; the waveforms and Gram matrices live in a scratch cached per shape).  Three
+    launches and nothing else on the device, no host synchronisation.'''
+    from .hparams import hparams
+    S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
+    B, C, T, F = src.shape
+    dev = src.device
+    ws = _neval_workspace(B, C, T, 2 * (F - 1), S, dev)
+    wav, G = ws[1], ws[2]
+    neval_synth(src, est, noise, gain, S, out=wav)
+    neval_gram(wav, out=G)
+    mean3, per_utt, perm_idx = neval_finalize(G, out=(torch.empty(B, 3, dtype=torch.float64, device=dev),
+                                                      torch.empty(B, dtype=torch.int32, device=dev),
+                                                      torch.empty(3, dtype=torch.float64, device=dev)))
+    return mean3[0], mean3[1], mean3[2], per_utt, perm_idx
+
+
 # ---- waveform training loss (include/danet_wavloss_hip.h) ---------------------------------------------
 # On the extension library libdanet_wavloss_hip.so, mapped at the first call: a run with TRAIN_LOSS null or
 # "pit-mse" never gets here.  Forward: reattach_phase -> metric_synth -> metric_gram (libdanet_metric_hip.so) ->
