@@ -11,13 +11,13 @@ Builds the fourteen HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_mix_hip.so           csrc/mix/*.hip           include/danet_mix_hip.h
     libdanet_speed_hip.so         csrc/speed/*.hip         include/danet_speed_hip.h
     libdanet_reverb_hip.so        csrc/reverb/*.hip        include/danet_reverb_hip.h
-    libdanet_metric_hip.so        csrc/metric/*.hip        include/danet_metric_hip.h
+    libdanet_metric_hip.so        csrc/metric/*.hip        include/danet_metric_hip.h, csrc/wave_metric.h
     libdanet_noise_hip.so         csrc/noise/*.hip         include/danet_noise_hip.h
     libdanet_level_hip.so         csrc/level/*.hip         include/danet_level_hip.h
-    libdanet_wavloss_hip.so       csrc/wavloss/*.hip       include/danet_wavloss_hip.h
+    libdanet_wavloss_hip.so       csrc/wavloss/*.hip       include/danet_wavloss_hip.h, csrc/wave_metric.h
     libdanet_gclip_hip.so         csrc/gclip/*.hip         include/danet_gclip_hip.h
     libdanet_dpcl_hip.so          csrc/dpcl/*.hip          include/danet_dpcl_hip.h
-    libdanet_neval_hip.so         csrc/neval/*.hip         include/danet_neval_hip.h
+    libdanet_neval_hip.so         csrc/neval/*.hip         include/danet_neval_hip.h, csrc/wave_metric.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -68,13 +68,13 @@ LATER_LIBRARIES = (REVERB,)
 REVERB_LIB = REVERB.out
 # build() stays the seven libraries above.  Every library after them goes HERE, appended: build_all() runs
 # build() and then over EXTENSIONS, and nothing pins the length of this tuple
-METRIC = _extension('metric')
+METRIC = _extension('metric', os.path.join(CSRC, 'wave_metric.h'))
 NOISE = _extension('noise')
 LEVEL = _extension('level')
-WAVLOSS = _extension('wavloss')
+WAVLOSS = _extension('wavloss', os.path.join(CSRC, 'wave_metric.h'))
 GCLIP = _extension('gclip')
 DPCL = _extension('dpcl')
-NEVAL = _extension('neval')
+NEVAL = _extension('neval', os.path.join(CSRC, 'wave_metric.h'))
 EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL, NEVAL)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out

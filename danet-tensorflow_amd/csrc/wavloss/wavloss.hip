@@ -3,14 +3,16 @@
  * finalize step that turns the metric's Gram matrices into -SI-SDR plus the pairing and the coefficients the
  * backward pass needs, and the adjoint of the metric's synthesis.  gfx950, wave64.
  *
- * danet_wavloss_fwd.  One workgroup; a thread per utterance does the 24-permutation search in float64 (the
- * arithmetic of danet_metric_si_sdr), the batch sums go over the metric's fixed tree, and a second pass of the
- * same thread over its own utterances writes pair and coef once the number of live utterances is known.
+ * The search, the batch sums' tree and the radix-2 stages are those of csrc/wave_metric.h, which
+ * libdanet_metric_hip.so runs too; this file adds the loss, the second pass and the backward kernel.
+ * danet_wavloss_fwd.  One workgroup; a thread per utterance runs pit_search, the batch sums go over
+ * block_sum_f64, and a second pass of the same thread over its own utterances writes pair and coef once the
+ * number of live utterances is known.
  * danet_wavloss_bwd.  One workgroup of 256 threads per (estimate, tile of frames).  LDS: N/2 twiddles
  * e^(-2 pi i j / N) (sincospif, once per workgroup), the tile's span of u, and the tile's frames of N floats.
  *   stage:  u[n] = (alpha s[n] + beta y[n]) / wsum[n] in float64, rounded once; wsum from the sample's own frames;
  *   frames: z[m] = w[2m] u[.. + 2m] + i w[2m+1] u[.. + 2m + 1], stored at the bit-reversed index of m;
- *   fft:    log2(N/2) in-place radix-2 stages (decimation in time) over all frames of the tile, one barrier each;
+ *   fft:    radix2_stages over all frames of the tile: with these twiddles, the forward transform;
  *   split:  X[k] = E - i e^(-2 pi i k / N) O with E = (Z[k] + conj(Z[N/2-k])) / 2, O = (Z[k] - conj(Z[N/2-k])) / 2;
  *           bins 0 and N/2 are Re Z[0] +- Im Z[0]; scaled by dloss c_k / N and written (through the phasor or not).
  */
@@ -19,6 +21,7 @@
 #include <stdio.h>
 
 #include "danet_wavloss_hip.h"
+#include "wave_metric.h"
 
 static thread_local char g_err[256] = "";
 
@@ -49,50 +52,9 @@ extern "C" int danet_wavloss_abi_version(void) { return DANET_WAVLOSS_ABI_VERSIO
     }                                                                                                   \
   } while (0)
 
-static const int kThreads = 256;
-static const int kWaves = kThreads / 64;
-static const int kMaxC = DANET_WAVLOSS_MAX_C;
+static_assert(kMaxC == DANET_WAVLOSS_MAX_C, "csrc/wave_metric.h and include/danet_wavloss_hip.h disagree");
 
 /* ------------------------------------------------------------------------------------- finalize */
-/* every lane: the sum over the workgroup, (w0 + w1) + (w2 + w3) of the waves' butterflies (the tree of
- * csrc/metric/metric.hip) */
-__device__ __forceinline__ double block_sum_f64(double v, double* part) {
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  __syncthreads();                                             /* (part may still be read from a call before) */
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-/* sdr(i, j) of the metric; *clamped: the value is one of the rule's clamps (its gradient is 0) */
-__device__ __forceinline__ double sdr_db(double a, double b, double c, bool* clamped) {
-  const double t = c * c / a, r = b - t;
-  *clamped = true;
-  if (!(t > 0.0)) return -100.0;
-  if (!(r > 0.0)) return 100.0;
-  const double d = 10.0 * log10(t / r);
-  if (d <= -100.0) return -100.0;
-  if (d >= 100.0) return 100.0;
-  *clamped = false;
-  return d;
-}
-
-/* the p-th permutation of range(C) in itertools.permutations order (csrc/pit_common.h) */
-__device__ __forceinline__ void nth_perm(int C, int p, int* out) {
-  int avail[kMaxC] = {0, 1, 2, 3};
-  int fact = 1;
-  for (int i = 2; i < C; ++i) fact *= i;
-  int n = C;
-  for (int i = 0; i < C; ++i) {
-    const int q = p / fact;
-    p -= q * fact;
-    out[i] = avail[q];
-    for (int j = q; j < n - 1; ++j) avail[j] = avail[j + 1];
-    --n;
-    if (n > 1) fact /= n;
-  }
-}
-
 __global__ __launch_bounds__(kThreads) void wavloss_fwd_kernel(int B, int C, const double* __restrict__ G,
                                                               double* __restrict__ loss_f64,
                                                               float* __restrict__ loss_f32,
@@ -102,39 +64,18 @@ __global__ __launch_bounds__(kThreads) void wavloss_fwd_kernel(int B, int C, con
                                                               double* __restrict__ coef) {
   __shared__ double part[kWaves];
   const int M = 2 * C;
-  int nperm = 1;
-  for (int i = 2; i <= C; ++i) nperm *= i;
   double sum_sdr = 0.0, live_utts = 0.0;
   for (int b = threadIdx.x; b < B; b += kThreads) {
-    const double* g = G + (int64_t)b * M * M;
-    double sdr[kMaxC][kMaxC];
-    bool live[kMaxC];
-    int n_live = 0;
-    for (int i = 0; i < C; ++i) {
-      const double a = g[i * M + i];
-      live[i] = a != 0.0;
-      if (!live[i]) continue;
-      ++n_live;
-      bool cl;
-      for (int j = 0; j < C; ++j) sdr[i][j] = sdr_db(a, g[(C + j) * M + (C + j)], g[i * M + (C + j)], &cl);
-    }
-    int best = 0;
-    double best_v = 0.0, u_sdr = 0.0;
-    if (n_live > 0) {
-      for (int p = 0; p < nperm; ++p) {
-        int perm[kMaxC];
-        nth_perm(C, p, perm);
-        double v = 0.0;
-        for (int i = 0; i < C; ++i)
-          if (live[i]) v += sdr[i][perm[i]];
-        if (p == 0 || v > best_v) { best = p; best_v = v; }
-      }
-      u_sdr = best_v / (double)n_live;
+    PitSearch s;
+    pit_search(G + (int64_t)b * M * M, M, C, s, NoBase());
+    double u_sdr = 0.0;
+    if (s.n_live > 0) {
+      u_sdr = s.best_v / (double)s.n_live;
       sum_sdr += u_sdr;
       live_utts += 1.0;
     }
     per_utt[b] = u_sdr;
-    perm_idx[b] = best;
+    perm_idx[b] = s.best;
   }
   const double ts = block_sum_f64(sum_sdr, part);
   const double tn = block_sum_f64(live_utts, part);
@@ -150,14 +91,16 @@ __global__ __launch_bounds__(kThreads) void wavloss_fwd_kernel(int B, int C, con
     const double* g = G + (int64_t)b * M * M;
     int n_live = 0;
     for (int i = 0; i < C; ++i) n_live += g[i * M + i] != 0.0 ? 1 : 0;
-    int perm[kMaxC];
-    nth_perm(C, perm_idx[b], perm);
-    int pr[kMaxC] = {-1, -1, -1, -1};
+    const unsigned perm = nth_perm(C, perm_idx[b]);
+    unsigned pr = 0xffffu;                                     /* estimate j -> its live reference, 15: none */
     for (int i = 0; i < C; ++i)
-      if (g[i * M + i] != 0.0) pr[perm[i]] = i;
+      if (g[i * M + i] != 0.0) {
+        const int sh = 4 * perm_at(perm, i);
+        pr = (pr & ~(15u << sh)) | ((unsigned)i << sh);
+      }
     for (int j = 0; j < C; ++j) {
       double alpha = 0.0, beta = 0.0;
-      const int i = pr[j];
+      const int i = perm_at(pr, j) < C ? perm_at(pr, j) : -1;
       if (i >= 0) {
         const double a = g[i * M + i], bb = g[(C + j) * M + (C + j)], c = g[i * M + (C + j)];
         bool cl;
@@ -205,11 +148,6 @@ struct BwdArgs {
   int log2_half;     /* log2(N/2) */
   int frames, tiles; /* frames per tile, tiles per estimate */
 };
-
-__device__ __forceinline__ int floor_div(int a, int b) {      /* b > 0 */
-  const int q = a / b;
-  return (a % b < 0) ? q - 1 : q;
-}
 
 __global__ __launch_bounds__(kThreads) void wavloss_bwd_kernel(BwdArgs a) {
   extern __shared__ __align__(16) float lds[];                 /* (viewed as float2 below) */
@@ -281,23 +219,8 @@ __global__ __launch_bounds__(kThreads) void wavloss_bwd_kernel(BwdArgs a) {
   }
   __syncthreads();
 
-  /* in-place radix-2 forward transform (decimation in time) of every frame of the tile */
-  const int half_m = M >> 1;
-  for (int lh = 0; lh < a.log2_half; ++lh) {
-    const int h = 1 << lh;
-    for (int idx = tid; idx < nfr * half_m; idx += kThreads) {
-      const int f = idx >> (a.log2_half - 1), p = idx & (half_m - 1);
-      const int pos = p & (h - 1);
-      const int i0 = ((p >> lh) << (lh + 1)) + pos;
-      float2* z = reinterpret_cast<float2*>(frames + f * N);
-      const float2 w = tw[pos << (a.log2_half - lh)];           /* e^(-2 pi i pos / 2h) */
-      const float2 x0 = z[i0], x1 = z[i0 + h];
-      const float vr = x1.x * w.x - x1.y * w.y, vi = x1.x * w.y + x1.y * w.x;
-      z[i0] = make_float2(x0.x + vr, x0.y + vi);
-      z[i0 + h] = make_float2(x0.x - vr, x0.y - vi);
-    }
-    __syncthreads();
-  }
+  /* the forward transform of every frame of the tile */
+  radix2_stages(frames, tw, nfr, N, a.log2_half);
 
   /* split step, scale, write: one output element per thread and turn */
   const float dl = a.dloss ? a.dloss[0] : 1.f;
@@ -355,8 +278,7 @@ extern "C" int danet_wavloss_bwd(void* stream, int B, int C, int T, int N, int S
   a.wav = wav; a.pair = pair; a.coef = coef; a.window = window; a.dloss = dloss;
   a.phasor = (const float2*)phasor; a.out = out;
   a.C = C; a.T = T; a.N = N; a.S = S;
-  a.log2_half = 0;
-  while ((2 << a.log2_half) < N) ++a.log2_half;
+  a.log2_half = log2_half(N);
   a.frames = frames; a.tiles = tiles;
   /* twiddles N + frames * N + span (frames - 1) * S + N floats: <= 3N/2 (1 + frames) <= 16384 at S = N/2 */
   const size_t lds_bytes = ((size_t)N + (size_t)frames * N + (size_t)(frames - 1) * S + N) * sizeof(float);

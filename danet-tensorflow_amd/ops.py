@@ -830,30 +830,62 @@ def _metric_window(dev):
     return t
 
 
-def _metric_workspace(B, C, T, N, S, dev):
-    '''(buffer, wav, G, per_utt, mean2, perm_idx): the views one shape cuts out of the grow-only scratch of this
-    (device, stream), in the layout of danet_metric_workspace_bytes; cached per shape'''
+def _wave_call(tag, name, *args):
+    '''danet_<tag>_<name>(*args) on the library of that tag (metric or neval), its status checked'''
+    lib = getattr(_lib, 'load_' + tag)()
+    getattr(_lib, tag + '_check')(getattr(lib, 'danet_%s_%s' % (tag, name))(*args))
+
+
+def _wave_workspace(tag, cache, rows, outs, B, C, T, N, S, dev):
+    '''(buffer, wav, G, per_utt, means, perm_idx): the views one shape cuts out of the grow-only scratch `tag` of this
+    (device, stream), in the layout of danet_<tag>_workspace_bytes -- `rows` signals and `outs` figures per
+    utterance; cached per shape in `cache`'''
     key = (dev.index if dev.index is not None else torch.cuda.current_device(),
            torch.cuda.current_stream().cuda_stream, B, C, T, N, S)
-    hit = _metric_ws.get(key)
-    if hit is not None and _lib._ws.get(key[:2] + ('metric',)) is hit[0]:
+    hit = cache.get(key)
+    if hit is not None and _lib._ws.get(key[:2] + (tag,)) is hit[0]:
         return hit
-    nbytes = _lib.load_metric().danet_metric_workspace_bytes(B, C, T, N, S)
+    nbytes = getattr(getattr(_lib, 'load_' + tag)(), 'danet_%s_workspace_bytes' % tag)(B, C, T, N, S)
     if nbytes == ctypes.c_size_t(-1).value:
-        _lib.metric_check(-1)
-    buf = _lib.workspace(nbytes, dev, 'metric')
-    M, Ls = 2 * C, (T - 1) * S
+        getattr(_lib, tag + '_check')(-1)
+    buf = _lib.workspace(nbytes, dev, tag)
+    Ls = (T - 1) * S
     views, off = [], 0
-    for shape, dtype, size in (((B, M, Ls), torch.float32, 4), ((B, M, M), torch.float64, 8),
-                               ((B, 2), torch.float64, 8), ((2,), torch.float64, 8), ((B,), torch.int32, 4)):
+    for shape, dtype, size in (((B, rows, Ls), torch.float32, 4), ((B, rows, rows), torch.float64, 8),
+                               ((B, outs), torch.float64, 8), ((outs,), torch.float64, 8), ((B,), torch.int32, 4)):
         n = int(np.prod(shape)) * size
         views.append(buf[off:off + n].view(dtype).view(shape))
         off += (n + 255) & ~255
     assert off == nbytes, (off, nbytes)
-    if len(_metric_ws) >= 64:
-        _metric_ws.clear()
-    hit = _metric_ws[key] = (buf,) + tuple(views)
+    if len(cache) >= 64:
+        cache.clear()
+    hit = cache[key] = (buf,) + tuple(views)
     return hit
+
+
+def _wave_gram(tag, wav, out):
+    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.is_contiguous()
+    B, M, Ls = wav.shape
+    if out is None:
+        out = torch.empty(B, M, M, dtype=torch.float64, device=wav.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B, M, M)
+    with _lib.timed(tag + '_gram'):
+        _wave_call(tag, 'gram', _lib.stream(), B, M, Ls, ptr(wav), ptr(out))
+    return out
+
+
+def _wave_finalize(tag, outs, G, out):
+    '''G [B, M, M], M = 2C + outs - 2 -> (means [outs], per_utt [B, outs], perm_idx int32 [B])'''
+    assert G.is_cuda and G.dtype == torch.float64 and G.dim() == 3 and G.is_contiguous() and G.shape[1] == G.shape[2]
+    B, M = G.shape[0], G.shape[1]
+    assert M % 2 == outs - 2, M
+    if out is None:
+        out = (torch.empty(B, outs, dtype=torch.float64, device=G.device),
+               torch.empty(B, dtype=torch.int32, device=G.device), torch.empty(outs, dtype=torch.float64, device=G.device))
+    per_utt, perm_idx, means = out
+    with _lib.timed(tag + '_si_sdr'):
+        _wave_call(tag, 'si_sdr', _lib.stream(), B, M // 2, ptr(G), ptr(per_utt), ptr(perm_idx), ptr(means))
+    return means, per_utt, perm_idx
 
 
 def metric_synth(src, est, fft_stride, window=None, out=None):
@@ -880,30 +912,13 @@ def metric_synth(src, est, fft_stride, window=None, out=None):
 def metric_gram(wav, out=None):
     '''float32 [B, M, Ls] -> float64 Gram matrices [B, M, M], ONE launch (danet_metric_gram: float64 products
     and sums over a fixed tree; symmetric bit for bit)'''
-    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.is_contiguous()
-    B, M, Ls = wav.shape
-    if out is None:
-        out = torch.empty(B, M, M, dtype=torch.float64, device=wav.device)
-    assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B, M, M)
-    with _lib.timed('metric_gram'):
-        _lib.metric_check(_lib.load_metric().danet_metric_gram(_lib.stream(), B, M, Ls, ptr(wav), ptr(out)))
-    return out
+    return _wave_gram('metric', wav, out)
 
 
 def metric_finalize(G, out=None):
     '''float64 Gram matrices [B, 2C, 2C] -> (mean2 [2], per_utt [B, 2], perm_idx int32 [B]), ONE launch
     (danet_metric_si_sdr); out: optional (per_utt, perm_idx, mean2) to write into'''
-    assert G.is_cuda and G.dtype == torch.float64 and G.dim() == 3 and G.is_contiguous() and G.shape[1] == G.shape[2]
-    B, M = G.shape[0], G.shape[1]
-    assert M % 2 == 0, M
-    if out is None:
-        out = (torch.empty(B, 2, dtype=torch.float64, device=G.device),
-               torch.empty(B, dtype=torch.int32, device=G.device), torch.empty(2, dtype=torch.float64, device=G.device))
-    per_utt, perm_idx, mean2 = out
-    with _lib.timed('metric_si_sdr'):
-        _lib.metric_check(_lib.load_metric().danet_metric_si_sdr(_lib.stream(), B, M // 2, ptr(G), ptr(per_utt),
-                                                                 ptr(perm_idx), ptr(mean2)))
-    return mean2, per_utt, perm_idx
+    return _wave_finalize('metric', 2, G, out)
 
 
 def si_sdr(src, est, fft_stride=None):
@@ -916,7 +931,7 @@ def si_sdr(src, est, fft_stride=None):
     S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
     B, C, T, F = src.shape
     dev = src.device
-    ws = _metric_workspace(B, C, T, 2 * (F - 1), S, dev)
+    ws = _wave_workspace('metric', _metric_ws, 2 * C, 2, B, C, T, 2 * (F - 1), S, dev)
     wav, G = ws[1], ws[2]
     metric_synth(src, est, S, out=wav)
     metric_gram(wav, out=G)
@@ -932,32 +947,6 @@ def si_sdr(src, est, fft_stride=None):
 # baseline of SI-SDRi is the mixture the model was given, sources + noise.
 NEVAL_MAX_C = 4                                      # DANET_NEVAL_MAX_C
 _neval_ws = {}           # (device index, stream, B, C, T, N, S) -> (scratch, wav, G, per_utt, mean3, perm_idx)
-
-
-def _neval_workspace(B, C, T, N, S, dev):
-    '''(buffer, wav, G, per_utt, mean3, perm_idx): the views one shape cuts out of the grow-only scratch of this
-    (device, stream), in the layout of danet_neval_workspace_bytes; cached per shape'''
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
-           torch.cuda.current_stream().cuda_stream, B, C, T, N, S)
-    hit = _neval_ws.get(key)
-    if hit is not None and _lib._ws.get(key[:2] + ('neval',)) is hit[0]:
-        return hit
-    nbytes = _lib.load_neval().danet_neval_workspace_bytes(B, C, T, N, S)
-    if nbytes == ctypes.c_size_t(-1).value:
-        _lib.neval_check(-1)
-    buf = _lib.workspace(nbytes, dev, 'neval')
-    M, Ls = 2 * C + 1, (T - 1) * S
-    views, off = [], 0
-    for shape, dtype, size in (((B, M, Ls), torch.float32, 4), ((B, M, M), torch.float64, 8),
-                               ((B, 3), torch.float64, 8), ((3,), torch.float64, 8), ((B,), torch.int32, 4)):
-        n = int(np.prod(shape)) * size
-        views.append(buf[off:off + n].view(dtype).view(shape))
-        off += (n + 255) & ~255
-    assert off == nbytes, (off, nbytes)
-    if len(_neval_ws) >= 64:
-        _neval_ws.clear()
-    hit = _neval_ws[key] = (buf,) + tuple(views)
-    return hit
 
 
 def neval_synth(src, est, noise, gain, fft_stride, window=None, out=None):
@@ -990,30 +979,13 @@ def neval_synth(src, est, noise, gain, fft_stride, window=None, out=None):
 def neval_gram(wav, out=None):
     '''float32 [B, M, Ls], M <= 9 -> float64 Gram matrices [B, M, M], ONE launch (danet_neval_gram: the tree of
     danet_metric_gram; symmetric bit for bit)'''
-    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.is_contiguous()
-    B, M, Ls = wav.shape
-    if out is None:
-        out = torch.empty(B, M, M, dtype=torch.float64, device=wav.device)
-    assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B, M, M)
-    with _lib.timed('neval_gram'):
-        _lib.neval_check(_lib.load_neval().danet_neval_gram(_lib.stream(), B, M, Ls, ptr(wav), ptr(out)))
-    return out
+    return _wave_gram('neval', wav, out)
 
 
 def neval_finalize(G, out=None):
     '''float64 Gram matrices [B, 2C + 1, 2C + 1] -> (mean3 [3], per_utt [B, 3], perm_idx int32 [B]): SI-SDR, SI-SDRi
     against the noisy mixture, nSNR; ONE launch (danet_neval_si_sdr); out: optional (per_utt, perm_idx, mean3)'''
-    assert G.is_cuda and G.dtype == torch.float64 and G.dim() == 3 and G.is_contiguous() and G.shape[1] == G.shape[2]
-    B, M = G.shape[0], G.shape[1]
-    assert M % 2 == 1, M
-    if out is None:
-        out = (torch.empty(B, 3, dtype=torch.float64, device=G.device),
-               torch.empty(B, dtype=torch.int32, device=G.device), torch.empty(3, dtype=torch.float64, device=G.device))
-    per_utt, perm_idx, mean3 = out
-    with _lib.timed('neval_si_sdr'):
-        _lib.neval_check(_lib.load_neval().danet_neval_si_sdr(_lib.stream(), B, (M - 1) // 2, ptr(G), ptr(per_utt),
-                                                              ptr(perm_idx), ptr(mean3)))
-    return mean3, per_utt, perm_idx
+    return _wave_finalize('neval', 3, G, out)
 
 
 def si_sdr_noisy(src, est, noise, gain=None, fft_stride=None):
@@ -1027,7 +999,7 @@ def si_sdr_noisy(src, est, noise, gain=None, fft_stride=None):
     S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
     B, C, T, F = src.shape
     dev = src.device
-    ws = _neval_workspace(B, C, T, 2 * (F - 1), S, dev)
+    ws = _wave_workspace('neval', _neval_ws, 2 * C + 1, 3, B, C, T, 2 * (F - 1), S, dev)
     wav, G = ws[1], ws[2]
     neval_synth(src, est, noise, gain, S, out=wav)
     neval_gram(wav, out=G)

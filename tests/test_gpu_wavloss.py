@@ -143,6 +143,55 @@ def test_fwd_clamps_ties_silence_and_an_utterance_free_batch():
     assert loss == 0.0 and not ref['coef'].any() and (ref['pair'] == -1).all()
 
 
+_METRIC_BATCH = {}
+
+
+def _metric_batch(C):
+    '''float64 Gram matrices [257, 2C, 2C] built on the host, once per C and never written again: W W^T of random
+    rows (positive definite), with the cases of the rule in utterances 1..5 made of small integers, so that their
+    entries are exact.  Utterance 0 is a plain one: a batch of it alone has a live reference.'''
+    if C not in _METRIC_BATCH:
+        rng = np.random.RandomState(40 + C)
+        B, L = 257, 6 * C
+        wav = rng.standard_normal((B, 2 * C, L)) * 10.0 ** rng.uniform(-2, 2, (B, 2 * C, 1))
+        wav[1:6] = rng.randint(-4, 5, (5, 2 * C, L))
+        wav[1:6, :, 0] = 1                                            # (no row of these is zero by chance)
+        wav[1, 0] = 0                                                 # a dead reference: zero diagonal
+        wav[2, :C] = 0                                                # every reference dead
+        wav[3, C:] = wav[3, C]                                        # equal estimates: all permutations tie
+        wav[4, C] = wav[4, 0]                                         # estimate 0 is reference 0: the +100 clamp
+        wav[5, C] = 0                                                 # a silent estimate: the -100 clamp
+        G = np.einsum('bin,bjn->bij', wav, wav)
+        assert G[1, 0, 0] == 0 and not G[2, :C, :C].any() and (np.diagonal(G[0], axis1=-2, axis2=-1) > 0).all()
+        assert MR.sdr(G[4, 0, 0], G[4, C, C], G[4, 0, C]) == 100.0 and MR.sdr(G[5, 0, 0], G[5, C, C], G[5, 0, C]) == -100.0
+        if C > 1:
+            sums = [sum(MR.sdr(G[3, i, i], G[3, C + p[i], C + p[i]], G[3, i, C + p[i]]) for i in range(C))
+                    for p in itertools.permutations(range(C))]
+            assert sums.count(max(sums)) >= 2                         # an exact tie between permutations
+        G.setflags(write=False)
+        _METRIC_BATCH[C] = G
+    return _METRIC_BATCH[C]
+
+
+@pytest.mark.parametrize('B', [1, 257])                              # 257: the per-thread utterance loop wraps once
+@pytest.mark.parametrize('C', [1, 2, 3, 4])
+def test_fwd_is_the_metric_finalize_bit_for_bit(C, B):
+    '''the loss is defined as the metric's: on one Gram batch danet_wavloss_fwd and danet_metric_si_sdr agree as
+    bits in the permutation, the SI-SDR of every utterance and (negated) the batch mean'''
+    from danet_amd import ops
+    G = torch.from_numpy(_metric_batch(C)[:B].copy()).cuda()
+    loss64, _, per_utt, perm_idx, _, _ = ops.wavloss_fwd(G)
+    mean2, m_per_utt, m_perm_idx = ops.metric_finalize(G)
+    torch.cuda.synchronize()
+    assert np.array_equal(_bits(perm_idx), _bits(m_perm_idx)), (perm_idx, m_perm_idx)
+    assert np.array_equal(_bits(per_utt), _bits(m_per_utt[:, 0]))
+    assert np.array_equal(_bits(loss64), _bits(-mean2[:1])), (loss64, mean2)
+    if B > 5:
+        got = per_utt.cpu().numpy()
+        assert got[2] == 0.0 and int(perm_idx[2]) == 0 and int(perm_idx[3]) == 0 and np.isfinite(got).all()
+        assert float(mean2[0]) != 0.0
+
+
 # ------------------------------------------------------------------------------------- backward
 def _frame_counts(N, S):
     tile = WR.tile_frames(N)

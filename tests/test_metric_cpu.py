@@ -57,6 +57,28 @@ def test_metric_library_exports_exactly_its_header():
         assert word not in out.stdout, word
 
 
+def test_the_wave_metric_core_is_defined_once_and_in_the_shared_header():
+    build = importlib.import_module('danet-tensorflow_amd._build')
+    csrc = os.path.join(ROOT, 'danet-tensorflow_amd', 'csrc')
+    shared = os.path.join(csrc, 'wave_metric.h')
+    files = [shared] + [os.path.join(csrc, n, n + '.hip') for n in ('metric', 'neval', 'wavloss')]
+    code = {f: re.sub(r'/\*.*?\*/', '', open(f).read(), flags=re.S) for f in files}
+    # radix2_stages: the radix-2 stage loop over all frames of a tile, of the synthesis and of wavloss_bwd_kernel
+    for name in ('floor_div', 'block_sum_f64', 'nth_perm', 'sdr_db', 'tiling_of', 'radix2_stages'):
+        # a definition: the name after a type, its parameter list, then a body
+        define = re.compile(r'[\w>&*]\s+%s\s*\([^;{}()]*\)\s*\{' % name)
+        counts = {f: len(define.findall(txt)) for f, txt in code.items()}
+        assert counts[shared] == 1 and sum(counts.values()) == 1, (name, counts)
+    for f in files[1:]:
+        assert '#include "wave_metric.h"' in code[f], f
+        assert re.search(r'\bblock_sum_f64\s*\(', code[f]), f                 # and every library uses the core
+    # its two callers: synth_tile in the header, wavloss_bwd_kernel
+    assert code[shared].count('radix2_stages(') == 2 and code[files[3]].count('radix2_stages(') == 1
+    for spec in (build.METRIC, build.NEVAL, build.WAVLOSS):
+        assert shared in spec.headers, spec.out
+        assert spec.headers[0] == os.path.join(ROOT, 'include', 'danet_%s_hip.h' % os.path.basename(spec.src_dir))
+
+
 def test_metric_prototypes_match_the_header_text():
     from danet_amd import _lib
     txt = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)

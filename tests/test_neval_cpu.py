@@ -135,6 +135,10 @@ def test_neval_library_reads_no_environment_and_allocates_nothing():
     for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new ', 'atomic'):
         assert word not in code, word
     assert 'fp contract(off)' in code                  # fl(g * z) is rounded before the split step adds it
+    shared = re.sub(r'/\*.*?\*/', '', open(os.path.join(os.path.dirname(d), 'wave_metric.h')).read(), flags=re.S)
+    assert '#include "wave_metric.h"' in code
+    for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new ', 'atomic'):
+        assert word not in shared, word
 
 
 def test_import_maps_nothing_and_a_missing_file_is_a_loud_error(tmp_path):

@@ -142,6 +142,10 @@ def test_wavloss_library_reads_no_environment_and_allocates_nothing():
     code = re.sub(r'/\*.*?\*/', '', open(os.path.join(d, 'wavloss.hip')).read(), flags=re.S)
     for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new ', 'atomic'):
         assert word not in code, word
+    shared = re.sub(r'/\*.*?\*/', '', open(os.path.join(os.path.dirname(d), 'wave_metric.h')).read(), flags=re.S)
+    assert '#include "wave_metric.h"' in code
+    for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new ', 'atomic'):
+        assert word not in shared, word
 
 
 def test_import_and_a_model_with_the_key_null_never_touch_the_library(tmp_path):

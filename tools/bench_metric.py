@@ -56,7 +56,7 @@ def entry_points_row(rounds, reps, B=32, C=2, T=128, N=256, S=64):
     hparams.digest()
     a, b, per_utt, perm = ops.si_sdr(src, est)                   # (maps the library, sizes the scratch)
     lib, st = _lib.load_metric(), _lib.stream()
-    _, wav, G, pu, mean2, pi = ops._metric_workspace(B, C, T, N, S, src.device)
+    _, wav, G, pu, mean2, pi = ops._wave_workspace('metric', ops._metric_ws, 2 * C, 2, B, C, T, N, S, src.device)
     w = ops._metric_window(src.device)
     one_G = torch.eye(2, dtype=torch.float64, device='cuda')[None].contiguous()
     one_out = torch.zeros(8, dtype=torch.float64, device='cuda')

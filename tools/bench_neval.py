@@ -66,8 +66,8 @@ def entry_points_row(rounds, reps, B=32, C=2, T=128, N=256, S=64):
     a, b, c, per_utt, perm = ops.si_sdr_noisy(src, est, noise, gain)     # (maps the library, sizes the scratch)
     ca, cb, cper, cperm = ops.si_sdr(src, est)
     nlib, mlib, st = _lib.load_neval(), _lib.load_metric(), _lib.stream()
-    _, wav, G, pu, mean3, pi = ops._neval_workspace(B, C, T, N, S, src.device)
-    _, mwav, mG, mpu, mean2, mpi = ops._metric_workspace(B, C, T, N, S, src.device)
+    _, wav, G, pu, mean3, pi = ops._wave_workspace('neval', ops._neval_ws, 2 * C + 1, 3, B, C, T, N, S, src.device)
+    _, mwav, mG, mpu, mean2, mpi = ops._wave_workspace('metric', ops._metric_ws, 2 * C, 2, B, C, T, N, S, src.device)
     w = ops._metric_window(src.device)
     one_G = torch.eye(3, dtype=torch.float64, device='cuda')[None].contiguous()
     one_out = torch.zeros(8, dtype=torch.float64, device='cuda')
