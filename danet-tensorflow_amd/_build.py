@@ -5,19 +5,21 @@ Builds the fourteen HIP libraries (gfx950 only) in-tree with hipcc.
 
     library (under csrc/)         sources                  rebuilt when one of these headers is newer
     libdanet_hip.so               csrc/*.hip, csrc/*.cpp   csrc/*.h, include/*.h
-    libdanet_conv_hip.so          csrc/conv/*.hip          include/danet_conv_hip.h, csrc/conv/*.h
-    libdanet_dropout_hip.so       csrc/dropout/*.hip       include/danet_dropout_hip.h
-    libdanet_prep_hip.so          csrc/prep/*.hip          include/danet_prep_hip.h
-    libdanet_mix_hip.so           csrc/mix/*.hip           include/danet_mix_hip.h
-    libdanet_speed_hip.so         csrc/speed/*.hip         include/danet_speed_hip.h
-    libdanet_reverb_hip.so        csrc/reverb/*.hip        include/danet_reverb_hip.h
-    libdanet_metric_hip.so        csrc/metric/*.hip        include/danet_metric_hip.h, csrc/wave_metric.h
-    libdanet_noise_hip.so         csrc/noise/*.hip         include/danet_noise_hip.h
-    libdanet_level_hip.so         csrc/level/*.hip         include/danet_level_hip.h
-    libdanet_wavloss_hip.so       csrc/wavloss/*.hip       include/danet_wavloss_hip.h, csrc/wave_metric.h
-    libdanet_gclip_hip.so         csrc/gclip/*.hip         include/danet_gclip_hip.h
-    libdanet_dpcl_hip.so          csrc/dpcl/*.hip          include/danet_dpcl_hip.h
-    libdanet_neval_hip.so         csrc/neval/*.hip         include/danet_neval_hip.h, csrc/wave_metric.h
+    libdanet_conv_hip.so          csrc/conv/*.hip          include/danet_conv_hip.h, csrc/conv/*.h, csrc/ext_core.h
+    libdanet_dropout_hip.so       csrc/dropout/*.hip       include/danet_dropout_hip.h, csrc/ext_core.h
+    libdanet_prep_hip.so          csrc/prep/*.hip          include/danet_prep_hip.h, csrc/ext_core.h
+    libdanet_mix_hip.so           csrc/mix/*.hip           include/danet_mix_hip.h,
+                                                           csrc/{ext_core,ragged_rows,sumsq_f64}.h
+    libdanet_speed_hip.so         csrc/speed/*.hip         include/danet_speed_hip.h, csrc/{ext_core,ragged_rows}.h
+    libdanet_reverb_hip.so        csrc/reverb/*.hip        include/danet_reverb_hip.h, csrc/{ext_core,ragged_rows}.h
+    libdanet_metric_hip.so        csrc/metric/*.hip        include/danet_metric_hip.h, csrc/{wave_metric,ext_core}.h
+    libdanet_noise_hip.so         csrc/noise/*.hip         include/danet_noise_hip.h, csrc/ext_core.h
+    libdanet_level_hip.so         csrc/level/*.hip         include/danet_level_hip.h, csrc/{ext_core,ragged_rows}.h
+    libdanet_wavloss_hip.so       csrc/wavloss/*.hip       include/danet_wavloss_hip.h, csrc/{wave_metric,ext_core}.h
+    libdanet_gclip_hip.so         csrc/gclip/*.hip         include/danet_gclip_hip.h,
+                                                           csrc/{ext_core,adam_one,sumsq_f64}.h
+    libdanet_dpcl_hip.so          csrc/dpcl/*.hip          include/danet_dpcl_hip.h, csrc/ext_core.h
+    libdanet_neval_hip.so         csrc/neval/*.hip         include/danet_neval_hip.h, csrc/{wave_metric,ext_core}.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -52,29 +54,33 @@ def _extension(name, *more_headers):
                    (os.path.join(INCLUDE, 'danet_%s_hip.h' % name),) + more_headers)
 
 
+def _shared(*names):
+    return tuple(os.path.join(CSRC, n + '.h') for n in names)
+
+
 CORE = Library(os.path.join(CSRC, 'libdanet_hip.so'), CSRC, (os.path.join(CSRC, '*.h'), os.path.join(INCLUDE, '*.h')))
-CONV = _extension('conv', os.path.join(CSRC, 'conv', '*.h'))
-DROPOUT = _extension('dropout')
-PREP = _extension('prep')
-MIX = _extension('mix')
-SPEED = _extension('speed')
+CONV = _extension('conv', os.path.join(CSRC, 'conv', '*.h'), *_shared('ext_core'))
+DROPOUT = _extension('dropout', *_shared('ext_core'))
+PREP = _extension('prep', *_shared('ext_core'))
+MIX = _extension('mix', *_shared('ext_core', 'ragged_rows', 'sumsq_f64'))
+SPEED = _extension('speed', *_shared('ext_core', 'ragged_rows'))
 # build() builds them in this order; a new record is APPENDED (the first five are indexed by position)
 LIBRARIES = (CORE, CONV, DROPOUT, PREP, MIX, SPEED)
 LIB, CONV_LIB, DROPOUT_LIB, PREP_LIB, MIX_LIB, SPEED_LIB = (spec.out for spec in LIBRARIES)
 # LIBRARIES stays the six records above; every library added after them goes HERE, appended, and build() runs
 # over LIBRARIES + LATER_LIBRARIES
-REVERB = _extension('reverb')
+REVERB = _extension('reverb', *_shared('ext_core', 'ragged_rows'))
 LATER_LIBRARIES = (REVERB,)
 REVERB_LIB = REVERB.out
 # build() stays the seven libraries above.  Every library after them goes HERE, appended: build_all() runs
 # build() and then over EXTENSIONS, and nothing pins the length of this tuple
-METRIC = _extension('metric', os.path.join(CSRC, 'wave_metric.h'))
-NOISE = _extension('noise')
-LEVEL = _extension('level')
-WAVLOSS = _extension('wavloss', os.path.join(CSRC, 'wave_metric.h'))
-GCLIP = _extension('gclip')
-DPCL = _extension('dpcl')
-NEVAL = _extension('neval', os.path.join(CSRC, 'wave_metric.h'))
+METRIC = _extension('metric', *_shared('wave_metric', 'ext_core'))
+NOISE = _extension('noise', *_shared('ext_core'))
+LEVEL = _extension('level', *_shared('ext_core', 'ragged_rows'))
+WAVLOSS = _extension('wavloss', *_shared('wave_metric', 'ext_core'))
+GCLIP = _extension('gclip', *_shared('ext_core', 'adam_one', 'sumsq_f64'))
+DPCL = _extension('dpcl', *_shared('ext_core'))
+NEVAL = _extension('neval', *_shared('wave_metric', 'ext_core'))
 EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL, NEVAL)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out

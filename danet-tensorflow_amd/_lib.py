@@ -384,6 +384,14 @@ def _check(spec, rc):
     raise DanetHipError('%s error %d: %s' % (spec.so[:-3], rc, msg.decode() if msg else '?'))
 
 
+def bytes_or_raise(nbytes, check):
+    '''the result of a library's *_workspace_bytes, or its error raised through that library's `check`:
+    (size_t)-1 says the arguments were refused and last_error says why'''
+    if nbytes == ctypes.c_size_t(-1).value:
+        check(-1)
+    return nbytes
+
+
 # Every load_*() answers from its global once that is set: load() runs at every kernel launch.
 def load():
     if _lib is not None:
@@ -404,10 +412,7 @@ def conv_check(rc):
 
 def conv_ws_bytes(op, desc):
     '''danet_conv_workspace_bytes(op, desc)'''
-    n = load_conv().danet_conv_workspace_bytes(op, ctypes.byref(desc))
-    if n == ctypes.c_size_t(-1).value:
-        conv_check(-1)
-    return n
+    return bytes_or_raise(load_conv().danet_conv_workspace_bytes(op, ctypes.byref(desc)), conv_check)
 
 
 def load_dropout():
@@ -629,10 +634,7 @@ def check(rc):
 def ws_bytes(op, *dims):
     '''danet_workspace_bytes(op, dims): scratch bytes of the entry point behind DANET_WS_<op>'''
     arr = (c_i64 * len(dims))(*[int(d) for d in dims])
-    n = load().danet_workspace_bytes(op, arr, len(dims))
-    if n == ctypes.c_size_t(-1).value:
-        check(-1)
-    return n
+    return bytes_or_raise(load().danet_workspace_bytes(op, arr, len(dims)), check)
 
 
 def ptr(t):

@@ -13,42 +13,11 @@
 //             one slab of (b, t) rows; every slab writes its own fp32 partial, a second kernel
 //             sums the slabs in a fixed order (deterministic, no atomics).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_conv_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-static thread_local char g_err[512] = "";
-
-static void conv_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_conv_last_error(void) { return g_err; }
-extern "C" int danet_conv_abi_version(void) { return DANET_CONV_ABI_VERSION; }
-
-#define CONV_CHECK_ARG(cond, ...)  \
-  do {                             \
-    if (!(cond)) {                 \
-      conv_set_error(__VA_ARGS__); \
-      return DANET_CONV_ERR_ARG;   \
-    }                              \
-  } while (0)
-
-#define CONV_CHECK_LAUNCH()                                                            \
-  do {                                                                                 \
-    hipError_t e__ = hipGetLastError();                                                \
-    if (e__ != hipSuccess) {                                                           \
-      conv_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e__), __FILE__, \
-                     __LINE__);                                                        \
-      return DANET_CONV_ERR_LAUNCH;                                                    \
-    }                                                                                  \
-  } while (0)
+#define DANET_EXT conv
+#define DANET_EXT_UPPER CONV
+#include "ext_core.h"
 
 typedef danet_conv_desc_t Desc;
 
@@ -343,21 +312,21 @@ __global__ __launch_bounds__(256) void conv_add_kernel(int64_t n, const float* a
 
 // ------------------------------------------------------------------ host
 static int check_desc(const Desc* d, const char* who) {
-  CONV_CHECK_ARG(d, "%s: null descriptor", who);
-  CONV_CHECK_ARG(d->k == 3 || d->k == 5, "%s: k must be 3 or 5 (got %d)", who, d->k);
-  CONV_CHECK_ARG(d->B >= 1 && d->T >= 1 && d->F >= 1, "%s: B, T, F must be >= 1", who);
-  CONV_CHECK_ARG(d->Cin >= 1 && d->Cin <= 64 && d->Cout >= 1 && d->Cout <= 64,
-                 "%s: Cin, Cout must be in [1, 64] (got %d, %d)", who, d->Cin, d->Cout);
-  CONV_CHECK_ARG(d->alpha >= 0.f && d->alpha < 1.f, "%s: alpha must be in [0, 1)", who);
-  CONV_CHECK_ARG((d->pool == 0 || d->pool == 1) && (d->d2s == 0 || d->d2s == 1) && !(d->pool && d->d2s),
-                 "%s: pool and d2s are 0/1 flags and exclusive", who);
-  CONV_CHECK_ARG(!d->pool || (d->T >= 2 && d->F >= 2), "%s: pool needs T, F >= 2", who);
-  CONV_CHECK_ARG(!d->d2s || d->Cout % 4 == 0, "%s: d2s needs Cout %% 4 == 0", who);
+  CHECK_ARG(d, "%s: null descriptor", who);
+  CHECK_ARG(d->k == 3 || d->k == 5, "%s: k must be 3 or 5 (got %d)", who, d->k);
+  CHECK_ARG(d->B >= 1 && d->T >= 1 && d->F >= 1, "%s: B, T, F must be >= 1", who);
+  CHECK_ARG(d->Cin >= 1 && d->Cin <= 64 && d->Cout >= 1 && d->Cout <= 64,
+            "%s: Cin, Cout must be in [1, 64] (got %d, %d)", who, d->Cin, d->Cout);
+  CHECK_ARG(d->alpha >= 0.f && d->alpha < 1.f, "%s: alpha must be in [0, 1)", who);
+  CHECK_ARG((d->pool == 0 || d->pool == 1) && (d->d2s == 0 || d->d2s == 1) && !(d->pool && d->d2s),
+            "%s: pool and d2s are 0/1 flags and exclusive", who);
+  CHECK_ARG(!d->pool || (d->T >= 2 && d->F >= 2), "%s: pool needs T, F >= 2", who);
+  CHECK_ARG(!d->d2s || d->Cout % 4 == 0, "%s: d2s needs Cout %% 4 == 0", who);
   for (int a = 0; a < 4; ++a)
-    CONV_CHECK_ARG(d->x_stride[a] >= 0 && d->y_stride[a] >= 0, "%s: negative stride", who);
-  CONV_CHECK_ARG((int64_t)d->B * ((d->T + 1) / 2) * ((d->F + 15) / 16) < (1LL << 31) / 4 &&
-                     (int64_t)d->B * d->T < (1LL << 31),
-                 "%s: too many pixels", who);
+    CHECK_ARG(d->x_stride[a] >= 0 && d->y_stride[a] >= 0, "%s: negative stride", who);
+  CHECK_ARG((int64_t)d->B * ((d->T + 1) / 2) * ((d->F + 15) / 16) < (1LL << 31) / 4 &&
+                (int64_t)d->B * d->T < (1LL << 31),
+            "%s: too many pixels", who);
   return DANET_CONV_OK;
 }
 
@@ -383,7 +352,7 @@ static int pixel_grid(const Desc& d) {
 
 extern "C" size_t danet_conv_workspace_bytes(int op, const danet_conv_desc_t* d) {
   if (op != DANET_CONV_WS_BWD_WEIGHT) {
-    conv_set_error("danet_conv_workspace_bytes: unknown op %d", op);
+    set_error("danet_conv_workspace_bytes: unknown op %d", op);
     return (size_t)-1;
   }
   if (check_desc(d, "danet_conv_workspace_bytes") != DANET_CONV_OK) return (size_t)-1;
@@ -395,11 +364,11 @@ extern "C" int danet_conv_fwd(void* stream, const danet_conv_desc_t* d, const fl
                               const float* bias, float* y, uint8_t* argmax) {
   const int rc = check_desc(d, "danet_conv_fwd");
   if (rc) return rc;
-  CONV_CHECK_ARG(x && w && bias && y, "danet_conv_fwd: null pointer");
-  CONV_CHECK_ARG(!d->pool || argmax, "danet_conv_fwd: pool needs argmax");
+  CHECK_ARG(x && w && bias && y, "danet_conv_fwd: null pointer");
+  CHECK_ARG(!d->pool || argmax, "danet_conv_fwd: pool needs argmax");
   CONV_DISPATCH(conv_fwd_kernel, d->k, ntiles(d->Cout), pixel_grid(*d), (hipStream_t)stream, *d, x, w, bias,
                 y, argmax);
-  CONV_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_CONV_OK;
 }
 
@@ -407,11 +376,11 @@ extern "C" int danet_conv_bwd_data(void* stream, const danet_conv_desc_t* d, con
                                    const uint8_t* argmax, const float* w, float* dx) {
   const int rc = check_desc(d, "danet_conv_bwd_data");
   if (rc) return rc;
-  CONV_CHECK_ARG(dy && y && w && dx, "danet_conv_bwd_data: null pointer");
-  CONV_CHECK_ARG(!d->pool || argmax, "danet_conv_bwd_data: pool needs argmax");
+  CHECK_ARG(dy && y && w && dx, "danet_conv_bwd_data: null pointer");
+  CHECK_ARG(!d->pool || argmax, "danet_conv_bwd_data: pool needs argmax");
   CONV_DISPATCH(conv_dgrad_kernel, d->k, ntiles(d->Cin), pixel_grid(*d), (hipStream_t)stream, *d, dy, y,
                 argmax, w, dx);
-  CONV_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_CONV_OK;
 }
 
@@ -420,30 +389,30 @@ extern "C" int danet_conv_bwd_weight(void* stream, const danet_conv_desc_t* d, c
                                      int accumulate, void* ws, size_t ws_bytes) {
   const int rc = check_desc(d, "danet_conv_bwd_weight");
   if (rc) return rc;
-  CONV_CHECK_ARG(x && dy && y && dw && db && ws, "danet_conv_bwd_weight: null pointer");
-  CONV_CHECK_ARG(!d->pool || argmax, "danet_conv_bwd_weight: pool needs argmax");
+  CHECK_ARG(x && dy && y && dw && db && ws, "danet_conv_bwd_weight: null pointer");
+  CHECK_ARG(!d->pool || argmax, "danet_conv_bwd_weight: pool needs argmax");
   const WgradPlan p = wgrad_plan(*d);
   if (ws_bytes < (size_t)p.nslab * p.Mtot * d->Cout * sizeof(float)) {
-    conv_set_error("danet_conv_bwd_weight: workspace too small");
+    set_error("danet_conv_bwd_weight: workspace too small");
     return DANET_CONV_ERR_WORKSPACE;
   }
   float* part = (float*)ws;
   const int grid = (int)(((int64_t)p.nslab * p.nmt + 3) / 4);
   CONV_DISPATCH(conv_wgrad_kernel, d->k, ntiles(d->Cout), grid, (hipStream_t)stream, *d, p, x, dy, y, argmax,
                 part);
-  CONV_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   const int n = p.Mtot * d->Cout;
   conv_wgrad_reduce_kernel<<<(n + 15) / 16, 256, 0, (hipStream_t)stream>>>(p, d->Cout, part, dw, db,
                                                                            accumulate ? 1 : 0);
-  CONV_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_CONV_OK;
 }
 
 extern "C" int danet_conv_add(void* stream, int64_t n, const float* a, const float* b, float* out) {
-  CONV_CHECK_ARG(n > 0 && a && b && out, "danet_conv_add: bad args");
+  CHECK_ARG(n > 0 && a && b && out, "danet_conv_add: bad args");
   int64_t g = (n + 255) / 256;
   const int grid = (int)(g < 4096 ? g : 4096);
   conv_add_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(n, a, b, out);
-  CONV_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_CONV_OK;
 }

@@ -12,45 +12,16 @@
  *
  * danet_dpcl_bwd.  The head kernels' shape: one row per thread in registers, A and Bm in LDS read as broadcasts.
  *
- * The libraries share no code: the XCD-aware (utterance, chunk) mapping of csrc/attractor.hip is restated here.
+ * The extension libraries share csrc/ext_core.h and nothing with the core library: the XCD-aware (utterance, chunk)
+ * mapping of csrc/attractor.hip is restated here.
  */
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_dpcl_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-static thread_local char g_err[256] = "";
-
-static void dpcl_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_dpcl_last_error(void) { return g_err; }
-extern "C" int danet_dpcl_abi_version(void) { return DANET_DPCL_ABI_VERSION; }
-
-#define DPCL_CHECK_ARG(cond, ...)   \
-  do {                              \
-    if (!(cond)) {                  \
-      dpcl_set_error(__VA_ARGS__);  \
-      return DANET_DPCL_ERR_ARG;    \
-    }                               \
-  } while (0)
-
-#define DPCL_CHECK_LAUNCH()                                                                          \
-  do {                                                                                               \
-    const hipError_t e_ = hipGetLastError();                                                         \
-    if (e_ != hipSuccess) {                                                                          \
-      dpcl_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return DANET_DPCL_ERR_LAUNCH;                                                                  \
-    }                                                                                                \
-  } while (0)
+#define DANET_EXT dpcl
+#define DANET_EXT_UPPER DPCL
+#include "ext_core.h"
 
 static const int kThreads = 256;
 static const int kTile = DANET_DPCL_TILE_ROWS;
@@ -66,8 +37,8 @@ static int64_t chunk_rows_of(int64_t N) { return kTile * cdiv64(cdiv64(N, DANET_
 static bool envelope_ok(const char* who, int B, int64_t N, int E, int C) {
   if (B < 1 || B > DANET_DPCL_MAX_B || N < 1 || N > DANET_DPCL_MAX_N || E < 1 || E > DANET_DPCL_MAX_E || C < 1 ||
       C > DANET_DPCL_MAX_C) {
-    dpcl_set_error("%s: need 1 <= B <= %d, 1 <= N <= 2^31, 1 <= E <= %d, 1 <= C <= %d (got B=%d N=%lld E=%d C=%d)", who,
-                   DANET_DPCL_MAX_B, DANET_DPCL_MAX_E, DANET_DPCL_MAX_C, B, (long long)N, E, C);
+    set_error("%s: need 1 <= B <= %d, 1 <= N <= 2^31, 1 <= E <= %d, 1 <= C <= %d (got B=%d N=%lld E=%d C=%d)", who,
+              DANET_DPCL_MAX_B, DANET_DPCL_MAX_E, DANET_DPCL_MAX_C, B, (long long)N, E, C);
     return false;
   }
   return true;
@@ -75,7 +46,7 @@ static bool envelope_ok(const char* who, int B, int64_t N, int E, int C) {
 
 extern "C" int danet_dpcl_chunks(int64_t N) {
   if (N < 1 || N > DANET_DPCL_MAX_N) {
-    dpcl_set_error("chunks: N must be in [1, 2^31] (got %lld)", (long long)N);
+    set_error("chunks: N must be in [1, 2^31] (got %lld)", (long long)N);
     return 0;
   }
   return (int)cdiv64(N, chunk_rows_of(N));
@@ -253,11 +224,11 @@ __global__ __launch_bounds__(kThreads) void dpcl_stats_kernel(int64_t N, int E, 
 extern "C" int danet_dpcl_stats(void* stream, int B, int64_t N, int E, int C, const float* embed, const float* src_pwr,
                                 void* workspace, size_t workspace_bytes) {
   if (!envelope_ok("stats", B, N, E, C)) return DANET_DPCL_ERR_ARG;
-  DPCL_CHECK_ARG(embed && src_pwr && workspace, "stats: null pointer");
-  DPCL_CHECK_ARG((((uintptr_t)embed | (uintptr_t)src_pwr | (uintptr_t)workspace) & 3) == 0,
-                 "stats: misaligned pointer (embed, src_pwr, workspace 4-byte)");
+  CHECK_ARG(embed && src_pwr && workspace, "stats: null pointer");
+  CHECK_ARG((((uintptr_t)embed | (uintptr_t)src_pwr | (uintptr_t)workspace) & 3) == 0,
+            "stats: misaligned pointer (embed, src_pwr, workspace 4-byte)");
   const size_t need = danet_dpcl_workspace_bytes(B, N, E, C);
-  DPCL_CHECK_ARG(workspace_bytes >= need, "stats: workspace too small (%zu bytes, need %zu)", workspace_bytes, need);
+  CHECK_ARG(workspace_bytes >= need, "stats: workspace too small (%zu bytes, need %zu)", workspace_bytes, need);
   const int64_t rows = chunk_rows_of(N);
   const dim3 grid((unsigned)cdiv64(N, rows), (unsigned)B);
   const bool vec = ((uintptr_t)embed & 15) == 0 && ((N * E) & 3) == 0;
@@ -267,7 +238,7 @@ extern "C" int danet_dpcl_stats(void* stream, int B, int64_t N, int E, int C, co
   else
     dpcl_stats_kernel<false><<<grid, kThreads, 0, (hipStream_t)stream>>>(N, E, C, rows, embed, src_pwr,
                                                                          (float*)workspace);
-  DPCL_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_DPCL_OK;
 }
 
@@ -341,19 +312,19 @@ extern "C" int danet_dpcl_finalize(void* stream, int B, int64_t N, int E, int C,
                                    size_t workspace_bytes, const float* main_f32, float alpha, double* per_utt_f64,
                                    float* dpcl_f32, float* total_f32, float* tables_f32, float* cs_f32) {
   if (!envelope_ok("finalize", B, N, E, C)) return DANET_DPCL_ERR_ARG;
-  DPCL_CHECK_ARG(workspace && per_utt_f64 && dpcl_f32 && total_f32 && tables_f32 && cs_f32, "finalize: null pointer");
-  DPCL_CHECK_ARG((((uintptr_t)workspace | (uintptr_t)main_f32 | (uintptr_t)dpcl_f32 | (uintptr_t)total_f32 |
-                   (uintptr_t)tables_f32 | (uintptr_t)cs_f32) & 3) == 0 && ((uintptr_t)per_utt_f64 & 7) == 0,
-                 "finalize: misaligned pointer (per_utt 8-byte, the rest 4-byte)");
-  DPCL_CHECK_ARG(isfinite(alpha) && alpha >= 0.f, "finalize: alpha must be finite and >= 0 (got %g)", (double)alpha);
+  CHECK_ARG(workspace && per_utt_f64 && dpcl_f32 && total_f32 && tables_f32 && cs_f32, "finalize: null pointer");
+  CHECK_ARG((((uintptr_t)workspace | (uintptr_t)main_f32 | (uintptr_t)dpcl_f32 | (uintptr_t)total_f32 |
+              (uintptr_t)tables_f32 | (uintptr_t)cs_f32) & 3) == 0 && ((uintptr_t)per_utt_f64 & 7) == 0,
+            "finalize: misaligned pointer (per_utt 8-byte, the rest 4-byte)");
+  CHECK_ARG(isfinite(alpha) && alpha >= 0.f, "finalize: alpha must be finite and >= 0 (got %g)", (double)alpha);
   const size_t need = danet_dpcl_workspace_bytes(B, N, E, C);
-  DPCL_CHECK_ARG(workspace_bytes >= need, "finalize: workspace too small (%zu bytes, need %zu)", workspace_bytes,
-                 need);
+  CHECK_ARG(workspace_bytes >= need, "finalize: workspace too small (%zu bytes, need %zu)", workspace_bytes,
+            need);
   const int nch = (int)cdiv64(N, chunk_rows_of(N));
   dpcl_finalize_kernel<<<1, kFinThreads, 0, (hipStream_t)stream>>>(B, nch, E, C, (const float*)workspace, main_f32,
                                                                    alpha, per_utt_f64, dpcl_f32, total_f32, tables_f32,
                                                                    cs_f32);
-  DPCL_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_DPCL_OK;
 }
 
@@ -452,11 +423,11 @@ extern "C" int danet_dpcl_bwd(void* stream, int B, int64_t N, int E, int C, cons
                               const float* tables_f32, const float* cs_f32, const float* dloss_f32, float scale,
                               float* dembed) {
   if (!envelope_ok("bwd", B, N, E, C)) return DANET_DPCL_ERR_ARG;
-  DPCL_CHECK_ARG(embed && src_pwr && tables_f32 && cs_f32 && dembed, "bwd: null pointer");
-  DPCL_CHECK_ARG((((uintptr_t)embed | (uintptr_t)src_pwr | (uintptr_t)tables_f32 | (uintptr_t)cs_f32 |
-                   (uintptr_t)dloss_f32 | (uintptr_t)dembed) & 3) == 0,
-                 "bwd: misaligned pointer (4-byte)");
-  DPCL_CHECK_ARG(isfinite(scale), "bwd: scale must be finite (got %g)", (double)scale);
+  CHECK_ARG(embed && src_pwr && tables_f32 && cs_f32 && dembed, "bwd: null pointer");
+  CHECK_ARG((((uintptr_t)embed | (uintptr_t)src_pwr | (uintptr_t)tables_f32 | (uintptr_t)cs_f32 |
+              (uintptr_t)dloss_f32 | (uintptr_t)dembed) & 3) == 0,
+            "bwd: misaligned pointer (4-byte)");
+  CHECK_ARG(isfinite(scale), "bwd: scale must be finite (got %g)", (double)scale);
   const dim3 grid((unsigned)cdiv64(N, kBwdRows), (unsigned)B);
   const bool vec = (((uintptr_t)embed | (uintptr_t)dembed) & 15) == 0 && (E & 3) == 0;
   hipStream_t st = (hipStream_t)stream;
@@ -465,6 +436,6 @@ extern "C" int danet_dpcl_bwd(void* stream, int B, int64_t N, int E, int C, cons
   else if (E <= 20) launch_bwd<20>(st, grid, vec, N, E, C, embed, src_pwr, tables_f32, cs_f32, dloss_f32, scale, dembed);
   else if (E <= 40) launch_bwd<40>(st, grid, vec, N, E, C, embed, src_pwr, tables_f32, cs_f32, dloss_f32, scale, dembed);
   else launch_bwd<64>(st, grid, vec, N, E, C, embed, src_pwr, tables_f32, cs_f32, dloss_f32, scale, dembed);
-  DPCL_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_DPCL_OK;
 }

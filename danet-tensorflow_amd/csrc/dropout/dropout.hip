@@ -11,32 +11,11 @@
  * from ONE division; indices are 32-bit unless rows * ld does not fit.
  */
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_dropout_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-static thread_local char g_err[256] = "";
-
-static void dropout_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_dropout_last_error(void) { return g_err; }
-extern "C" int danet_dropout_abi_version(void) { return DANET_DROPOUT_ABI_VERSION; }
-
-#define DROPOUT_CHECK_ARG(cond, ...)   \
-  do {                                 \
-    if (!(cond)) {                     \
-      dropout_set_error(__VA_ARGS__);  \
-      return DANET_DROPOUT_ERR_ARG;    \
-    }                                  \
-  } while (0)
+#define DANET_EXT dropout
+#define DANET_EXT_UPPER DROPOUT
+#include "ext_core.h"
 
 struct Philox {
   uint32_t w[4];
@@ -155,21 +134,21 @@ extern "C" int danet_dropout_apply(void* stream, int64_t rows, int64_t cols, con
                                    float* y, int64_t ldy, uint32_t threshold, float scale, uint32_t key0,
                                    uint32_t key1, uint32_t stream_id, uint32_t step) {
   const int64_t lim = (int64_t)1 << 62;
-  DROPOUT_CHECK_ARG(x != nullptr && y != nullptr, "dropout_apply: null pointer");
-  DROPOUT_CHECK_ARG(rows >= 1 && cols >= 1, "dropout_apply: rows and cols must be >= 1 (got %lld x %lld)",
-                    (long long)rows, (long long)cols);
-  DROPOUT_CHECK_ARG(ldx >= cols && ldy >= cols, "dropout_apply: ldx, ldy must be >= cols (%lld, %lld < %lld)",
-                    (long long)ldx, (long long)ldy, (long long)cols);
-  DROPOUT_CHECK_ARG(cols < lim / rows && ldx < lim / rows && ldy < lim / rows,
-                    "dropout_apply: rows * ld must be < 2^62");
-  DROPOUT_CHECK_ARG(((uintptr_t)x & 3) == 0 && ((uintptr_t)y & 3) == 0,
-                    "dropout_apply: x and y must be 4-byte aligned");
-  DROPOUT_CHECK_ARG(threshold >= 1, "dropout_apply: threshold must be >= 1 (0 keeps nothing)");
-  DROPOUT_CHECK_ARG(x != y || ldx == ldy, "dropout_apply: in place (x == y) needs ldx == ldy");
-  DROPOUT_CHECK_ARG(scale == scale && scale - scale == 0.f, "dropout_apply: scale must be finite");
+  CHECK_ARG(x != nullptr && y != nullptr, "dropout_apply: null pointer");
+  CHECK_ARG(rows >= 1 && cols >= 1, "dropout_apply: rows and cols must be >= 1 (got %lld x %lld)",
+            (long long)rows, (long long)cols);
+  CHECK_ARG(ldx >= cols && ldy >= cols, "dropout_apply: ldx, ldy must be >= cols (%lld, %lld < %lld)",
+            (long long)ldx, (long long)ldy, (long long)cols);
+  CHECK_ARG(cols < lim / rows && ldx < lim / rows && ldy < lim / rows,
+            "dropout_apply: rows * ld must be < 2^62");
+  CHECK_ARG(((uintptr_t)x & 3) == 0 && ((uintptr_t)y & 3) == 0,
+            "dropout_apply: x and y must be 4-byte aligned");
+  CHECK_ARG(threshold >= 1, "dropout_apply: threshold must be >= 1 (0 keeps nothing)");
+  CHECK_ARG(x != y || ldx == ldy, "dropout_apply: in place (x == y) needs ldx == ldy");
+  CHECK_ARG(scale == scale && scale - scale == 0.f, "dropout_apply: scale must be finite");
   const int cus = device_cus();
   if (cus <= 0) {
-    dropout_set_error("dropout_apply: no HIP device");
+    set_error("dropout_apply: no HIP device");
     return DANET_DROPOUT_ERR_LAUNCH;
   }
   DropArgs a;
@@ -197,10 +176,6 @@ extern "C" int danet_dropout_apply(void* stream, int64_t rows, int64_t cols, con
     if (small) dropout_scalar_kernel<uint32_t><<<grid, 256, 0, s>>>(a);
     else dropout_scalar_kernel<uint64_t><<<grid, 256, 0, s>>>(a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    dropout_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-    return DANET_DROPOUT_ERR_LAUNCH;
-  }
+  CHECK_LAUNCH();
   return DANET_DROPOUT_OK;
 }

@@ -23,39 +23,12 @@
  * (checked with -Rpass-analysis=kernel-resource-usage; tools/bench_level.py has the timings).
  */
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_level_hip.h"
-
-static thread_local char g_err[256] = "";
-
-static void level_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_level_last_error(void) { return g_err; }
-extern "C" int danet_level_abi_version(void) { return DANET_LEVEL_ABI_VERSION; }
-
-#define LEVEL_CHECK_ARG(cond, ...)   \
-  do {                               \
-    if (!(cond)) {                   \
-      level_set_error(__VA_ARGS__);  \
-      return DANET_LEVEL_ERR_ARG;    \
-    }                                \
-  } while (0)
-
-#define LEVEL_CHECK_LAUNCH()                                                                          \
-  do {                                                                                                \
-    const hipError_t e_ = hipGetLastError();                                                          \
-    if (e_ != hipSuccess) {                                                                           \
-      level_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return DANET_LEVEL_ERR_LAUNCH;                                                                  \
-    }                                                                                                 \
-  } while (0)
+#define DANET_EXT level
+#define DANET_EXT_UPPER LEVEL
+#include "ext_core.h"
+#include "ragged_rows.h"
 
 static const int kThreads = 256;
 static const int kThr = DANET_LEVEL_THRESHOLDS;
@@ -77,19 +50,14 @@ static int64_t tiles_of(int64_t max_len) {
 
 extern "C" size_t danet_level_workspace_bytes(int n_utt, int64_t max_len) {
   if (n_utt < 1 || max_len < 0 || max_len > kMaxLen || (int64_t)n_utt * tiles_of(max_len) >= ((int64_t)1 << 31)) {
-    level_set_error("workspace_bytes: need n_utt >= 1, 0 <= max_len <= 2^31 and n_utt * tiles per row < 2^31 "
-                    "(got %d, %lld)", n_utt, (long long)max_len);
+    set_error("workspace_bytes: need n_utt >= 1, 0 <= max_len <= 2^31 and n_utt * tiles per row < 2^31 "
+              "(got %d, %lld)", n_utt, (long long)max_len);
     return (size_t)-1;
   }
   return (size_t)n_utt * (size_t)tiles_of(max_len) * (kStateBytes + kRecInts * sizeof(int));
 }
 
-struct LevelArgs {
-  const float* pool;
-  int64_t pool_len;
-  const int64_t* offsets;
-  const int64_t* lengths;
-  int64_t max_len;
+struct LevelArgs : RowTable {
   int n_utt;
   int tiles;             /* tiles of a max_len row, >= 1 */
   double g, k;           /* k = 1 - g                    */
@@ -100,20 +68,6 @@ struct LevelArgs {
   double2* state;        /* [n_utt][tiles]               */
   int* rec;              /* [n_utt][tiles][3][kThr]      */
 };
-
-/* the row is clamped, never trusted: -> [off, off + len) inside the pool, 0 <= len <= max_len */
-__device__ __forceinline__ void clamp_row(const LevelArgs& a, int u, int64_t& off, int64_t& len) {
-  off = a.offsets[u];
-  len = a.lengths[u];
-  if (len < 0) len = 0;
-  if (off < 0) {
-    len = (off <= -len) ? 0 : len + off;      /* the part in front of the pool is cut off */
-    off = 0;
-  }
-  if (off > a.pool_len) off = a.pool_len;
-  if (len > a.pool_len - off) len = a.pool_len - off;
-  if (len > a.max_len) len = a.max_len;
-}
 
 /* thread -> (row u, tile t, its samples x[0..m)); false: no such tile in this row */
 __device__ __forceinline__ bool tile_of_thread(const LevelArgs& a, int& u, int& t, const float*& x, int& m) {
@@ -220,20 +174,20 @@ __global__ __launch_bounds__(kThreads) void level_rows_kernel(LevelArgs a) {
 extern "C" int danet_level_activity(void* stream, int n_utt, const float* pool, int64_t pool_len,
                                     const int64_t* offsets, const int64_t* lengths, int64_t max_len, double g,
                                     int64_t hang, const double* thr, int64_t* counts, void* ws, size_t ws_bytes) {
-  LEVEL_CHECK_ARG(n_utt >= 1, "activity: n_utt must be >= 1 (got %d)", n_utt);
-  LEVEL_CHECK_ARG(pool_len >= 0, "activity: pool_len must be >= 0");
-  LEVEL_CHECK_ARG(max_len >= 0 && max_len <= kMaxLen, "activity: max_len must be in [0, 2^31] (got %lld)",
-                  (long long)max_len);
-  LEVEL_CHECK_ARG(g > 0.0 && g < 1.0, "activity: g must be inside (0, 1) (got %g)", g);      /* (a NaN fails both) */
-  LEVEL_CHECK_ARG(hang >= 0 && hang <= kMaxHang, "activity: hang must be in [0, 2^40] (got %lld)", (long long)hang);
-  LEVEL_CHECK_ARG(pool && offsets && lengths && thr && counts && ws, "activity: null pointer");
-  LEVEL_CHECK_ARG(((uintptr_t)pool & 3) == 0 && ((uintptr_t)offsets & 7) == 0 && ((uintptr_t)lengths & 7) == 0 &&
-                      ((uintptr_t)thr & 7) == 0 && ((uintptr_t)counts & 7) == 0 && ((uintptr_t)ws & 15) == 0,
-                  "activity: misaligned pointer (pool 4-byte; offsets, lengths, thr, counts 8-byte; ws 16-byte)");
+  CHECK_ARG(n_utt >= 1, "activity: n_utt must be >= 1 (got %d)", n_utt);
+  CHECK_ARG(pool_len >= 0, "activity: pool_len must be >= 0");
+  CHECK_ARG(max_len >= 0 && max_len <= kMaxLen, "activity: max_len must be in [0, 2^31] (got %lld)",
+            (long long)max_len);
+  CHECK_ARG(g > 0.0 && g < 1.0, "activity: g must be inside (0, 1) (got %g)", g);      /* (a NaN fails both) */
+  CHECK_ARG(hang >= 0 && hang <= kMaxHang, "activity: hang must be in [0, 2^40] (got %lld)", (long long)hang);
+  CHECK_ARG(pool && offsets && lengths && thr && counts && ws, "activity: null pointer");
+  CHECK_ARG(((uintptr_t)pool & 3) == 0 && ((uintptr_t)offsets & 7) == 0 && ((uintptr_t)lengths & 7) == 0 &&
+                ((uintptr_t)thr & 7) == 0 && ((uintptr_t)counts & 7) == 0 && ((uintptr_t)ws & 15) == 0,
+            "activity: misaligned pointer (pool 4-byte; offsets, lengths, thr, counts 8-byte; ws 16-byte)");
   const int64_t tiles = tiles_of(max_len);
-  LEVEL_CHECK_ARG((int64_t)n_utt * tiles < ((int64_t)1 << 31), "activity: n_utt * tiles per row must be < 2^31");
+  CHECK_ARG((int64_t)n_utt * tiles < ((int64_t)1 << 31), "activity: n_utt * tiles per row must be < 2^31");
   const size_t need = danet_level_workspace_bytes(n_utt, max_len);
-  LEVEL_CHECK_ARG(ws_bytes >= need, "activity: workspace too small (%zu < %zu)", ws_bytes, need);
+  CHECK_ARG(ws_bytes >= need, "activity: workspace too small (%zu < %zu)", ws_bytes, need);
   LevelArgs a;
   a.pool = pool; a.pool_len = pool_len; a.offsets = offsets; a.lengths = lengths; a.max_len = max_len;
   a.n_utt = n_utt; a.tiles = (int)tiles; a.g = g; a.k = 1.0 - g; a.hang = hang; a.thr = thr; a.counts = counts;
@@ -247,12 +201,12 @@ extern "C" int danet_level_activity(void* stream, int n_utt, const float* pool, 
   const unsigned per_tile = (unsigned)(((int64_t)n_utt * tiles + kThreads - 1) / kThreads);
   const hipStream_t s = (hipStream_t)stream;
   level_state_kernel<<<dim3(per_tile), kThreads, 0, s>>>(a);
-  LEVEL_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   level_carry_kernel<<<dim3((unsigned)((n_utt + kThreads - 1) / kThreads)), kThreads, 0, s>>>(a);
-  LEVEL_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   level_count_kernel<<<dim3(per_tile), kThreads, 0, s>>>(a);
-  LEVEL_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   level_rows_kernel<<<dim3((unsigned)(((int64_t)n_utt * kThr + kThreads - 1) / kThreads)), kThreads, 0, s>>>(a);
-  LEVEL_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_LEVEL_OK;
 }

@@ -11,40 +11,12 @@
  * from the same matrix by linearity: <m, m> = sum_kl G[k][l], <m, s_i> = sum_k G[k][i].  Two outputs per utterance.
  */
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_metric_hip.h"
+#define DANET_EXT metric
+#define DANET_EXT_UPPER METRIC
+#include "ext_core.h"
 #include "wave_metric.h"
-
-static thread_local char g_err[256] = "";
-
-static void metric_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_metric_last_error(void) { return g_err; }
-extern "C" int danet_metric_abi_version(void) { return DANET_METRIC_ABI_VERSION; }
-
-#define METRIC_CHECK_ARG(cond, ...)   \
-  do {                                \
-    if (!(cond)) {                    \
-      metric_set_error(__VA_ARGS__);  \
-      return DANET_METRIC_ERR_ARG;    \
-    }                                 \
-  } while (0)
-
-#define METRIC_CHECK_LAUNCH()                                                                          \
-  do {                                                                                                 \
-    const hipError_t e_ = hipGetLastError();                                                           \
-    if (e_ != hipSuccess) {                                                                            \
-      metric_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return DANET_METRIC_ERR_LAUNCH;                                                                  \
-    }                                                                                                  \
-  } while (0)
 
 static_assert(kMaxC == DANET_METRIC_MAX_C, "csrc/wave_metric.h and include/danet_metric_hip.h disagree");
 
@@ -67,8 +39,8 @@ __global__ __launch_bounds__(kThreads) void metric_synth_kernel(MetricSynthArgs 
 
 extern "C" size_t danet_metric_workspace_bytes(int B, int C, int T, int N, int S) {
   if (!synth_shape_ok(B, C, T, N, S) || C > kMaxC) {
-    metric_set_error("workspace_bytes: need B >= 1, 1 <= C <= %d, T >= 2, N a power of two in 64..1024 and "
-                     "N/8 <= S <= N/2 (got %d, %d, %d, %d, %d)", kMaxC, B, C, T, N, S);
+    set_error("workspace_bytes: need B >= 1, 1 <= C <= %d, T >= 2, N a power of two in 64..1024 and "
+              "N/8 <= S <= N/2 (got %d, %d, %d, %d, %d)", kMaxC, B, C, T, N, S);
     return (size_t)-1;
   }
   const size_t Ls = (size_t)(T - 1) * (size_t)S, M = 2 * (size_t)C;
@@ -79,22 +51,22 @@ extern "C" size_t danet_metric_workspace_bytes(int B, int C, int T, int N, int S
 
 extern "C" int danet_metric_synth(void* stream, int B, int C, int T, int N, int S, const float* ref_c64,
                                   const float* est_c64, const float* window, float* wav) {
-  METRIC_CHECK_ARG(B >= 1 && C >= 1, "synth: B and C must be >= 1 (got %d, %d)", B, C);
-  METRIC_CHECK_ARG(T >= 2, "synth: T must be >= 2 (got %d)", T);
-  METRIC_CHECK_ARG(N >= 64 && N <= 1024 && (N & (N - 1)) == 0, "synth: N must be a power of two in 64..1024 (got %d)",
-                   N);
-  METRIC_CHECK_ARG(S >= 1 && 2 * (int64_t)S <= N && 8 * (int64_t)S >= N, "synth: S must be in [N/8, N/2] (got %d at N = %d)",
-                   S, N);
-  METRIC_CHECK_ARG(ref_c64 && est_c64 && window && wav, "synth: null pointer");
-  METRIC_CHECK_ARG(((uintptr_t)ref_c64 & 7) == 0 && ((uintptr_t)est_c64 & 7) == 0 && ((uintptr_t)window & 3) == 0 &&
-                       ((uintptr_t)wav & 3) == 0,
-                   "synth: misaligned pointer (ref, est 8-byte; window, wav 4-byte)");
-  METRIC_CHECK_ARG((int64_t)(T - 1) * S < ((int64_t)1 << 31), "synth: (T - 1) * S must be < 2^31");
+  CHECK_ARG(B >= 1 && C >= 1, "synth: B and C must be >= 1 (got %d, %d)", B, C);
+  CHECK_ARG(T >= 2, "synth: T must be >= 2 (got %d)", T);
+  CHECK_ARG(N >= 64 && N <= 1024 && (N & (N - 1)) == 0, "synth: N must be a power of two in 64..1024 (got %d)",
+            N);
+  CHECK_ARG(S >= 1 && 2 * (int64_t)S <= N && 8 * (int64_t)S >= N, "synth: S must be in [N/8, N/2] (got %d at N = %d)",
+            S, N);
+  CHECK_ARG(ref_c64 && est_c64 && window && wav, "synth: null pointer");
+  CHECK_ARG(((uintptr_t)ref_c64 & 7) == 0 && ((uintptr_t)est_c64 & 7) == 0 && ((uintptr_t)window & 3) == 0 &&
+                ((uintptr_t)wav & 3) == 0,
+            "synth: misaligned pointer (ref, est 8-byte; window, wav 4-byte)");
+  CHECK_ARG((int64_t)(T - 1) * S < ((int64_t)1 << 31), "synth: (T - 1) * S must be < 2^31");
   const MetricSynthArgs a = {(const float2*)ref_c64, (const float2*)est_c64, synth_args(C, T, N, S, window, wav)};
   const int64_t blocks = (int64_t)B * 2 * C * a.s.tiles;
-  METRIC_CHECK_ARG(blocks < ((int64_t)1 << 31), "synth: B * 2C * tiles must be < 2^31");
+  CHECK_ARG(blocks < ((int64_t)1 << 31), "synth: B * 2C * tiles must be < 2^31");
   metric_synth_kernel<<<dim3((unsigned)blocks), kThreads, synth_lds_bytes(a.s), (hipStream_t)stream>>>(a);
-  METRIC_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_METRIC_OK;
 }
 
@@ -107,15 +79,15 @@ __global__ __launch_bounds__(kThreads) void metric_gram_kernel(int M, int n_pair
 }
 
 extern "C" int danet_metric_gram(void* stream, int B, int M, int64_t Ls, const float* wav, double* G) {
-  METRIC_CHECK_ARG(B >= 1, "gram: B must be >= 1 (got %d)", B);
-  METRIC_CHECK_ARG(M >= 1 && M <= 2 * kMaxC, "gram: M must be in 1..%d (got %d)", 2 * kMaxC, M);
-  METRIC_CHECK_ARG(Ls >= 1 && Ls < ((int64_t)1 << 31), "gram: Ls must be in [1, 2^31) (got %lld)", (long long)Ls);
-  METRIC_CHECK_ARG(wav && G, "gram: null pointer");
-  METRIC_CHECK_ARG(((uintptr_t)wav & 3) == 0 && ((uintptr_t)G & 7) == 0, "gram: misaligned pointer (wav 4-byte, G 8-byte)");
+  CHECK_ARG(B >= 1, "gram: B must be >= 1 (got %d)", B);
+  CHECK_ARG(M >= 1 && M <= 2 * kMaxC, "gram: M must be in 1..%d (got %d)", 2 * kMaxC, M);
+  CHECK_ARG(Ls >= 1 && Ls < ((int64_t)1 << 31), "gram: Ls must be in [1, 2^31) (got %lld)", (long long)Ls);
+  CHECK_ARG(wav && G, "gram: null pointer");
+  CHECK_ARG(((uintptr_t)wav & 3) == 0 && ((uintptr_t)G & 7) == 0, "gram: misaligned pointer (wav 4-byte, G 8-byte)");
   const int n_pairs = M * (M + 1) / 2;
-  METRIC_CHECK_ARG((int64_t)B * n_pairs < ((int64_t)1 << 31), "gram: B * M * (M + 1) / 2 must be < 2^31");
+  CHECK_ARG((int64_t)B * n_pairs < ((int64_t)1 << 31), "gram: B * M * (M + 1) / 2 must be < 2^31");
   metric_gram_kernel<<<dim3((unsigned)((int64_t)B * n_pairs)), kThreads, 0, (hipStream_t)stream>>>(M, n_pairs, Ls, wav, G);
-  METRIC_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_METRIC_OK;
 }
 
@@ -161,13 +133,13 @@ __global__ __launch_bounds__(kThreads) void metric_si_sdr_kernel(int B, int C, c
 
 extern "C" int danet_metric_si_sdr(void* stream, int B, int C, const double* G, double* per_utt, int32_t* perm_idx,
                                    double* mean2) {
-  METRIC_CHECK_ARG(B >= 1, "si_sdr: B must be >= 1 (got %d)", B);
-  METRIC_CHECK_ARG(C >= 1 && C <= kMaxC, "si_sdr: C must be in 1..%d (got %d)", kMaxC, C);
-  METRIC_CHECK_ARG(G && per_utt && perm_idx && mean2, "si_sdr: null pointer");
-  METRIC_CHECK_ARG(((uintptr_t)G & 7) == 0 && ((uintptr_t)per_utt & 7) == 0 && ((uintptr_t)mean2 & 7) == 0 &&
-                       ((uintptr_t)perm_idx & 3) == 0,
-                   "si_sdr: misaligned pointer (G, per_utt, mean2 8-byte; perm_idx 4-byte)");
+  CHECK_ARG(B >= 1, "si_sdr: B must be >= 1 (got %d)", B);
+  CHECK_ARG(C >= 1 && C <= kMaxC, "si_sdr: C must be in 1..%d (got %d)", kMaxC, C);
+  CHECK_ARG(G && per_utt && perm_idx && mean2, "si_sdr: null pointer");
+  CHECK_ARG(((uintptr_t)G & 7) == 0 && ((uintptr_t)per_utt & 7) == 0 && ((uintptr_t)mean2 & 7) == 0 &&
+                ((uintptr_t)perm_idx & 3) == 0,
+            "si_sdr: misaligned pointer (G, per_utt, mean2 8-byte; perm_idx 4-byte)");
   metric_si_sdr_kernel<<<dim3(1), kThreads, 0, (hipStream_t)stream>>>(B, C, G, per_utt, perm_idx, mean2);
-  METRIC_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_METRIC_OK;
 }

@@ -5,11 +5,10 @@
  * danet_mix_power.  One workgroup of 256 threads per (row, slice); a slice is
  * max(65536, ceil4(max_len / 256)) samples, so a row of millions of samples is spread over up to 256
  * workgroups while a short row costs one, and thousands of rows go in ONE launch (grid = rows x
- * slices; a workgroup whose slice starts beyond its row returns before it loads anything).  A thread
- * walks its 16-byte vectors at stride 256, four loads in flight, adds the four exact float64 squares
- * of a vector as (a + b) + (c + d) and that to its accumulator; the workgroup sum is a fixed
- * butterfly over the 64 lanes of a wave (cross-lane moves, no LDS) and (w0 + w1) + (w2 + w3) over
- * the four waves through LDS.  Longest chain of additions: slice / 1024 + 2 (thread) + 2 (head,
+ * slices; a workgroup whose slice starts beyond its row returns before it loads anything).  The row
+ * is clamped by clamp_row of csrc/ragged_rows.h; a slice's sum is that of csrc/sumsq_f64.h, which
+ * describes it: slice_sumsq per thread, wave_sums, and thread 0 adds the four wave sums as
+ * (w0 + w1) + (w2 + w3).  Longest chain of additions: slice / 1024 + 2 (thread) + 2 (head,
  * tail) + 8 (workgroup) + slices (second launch) <= 2^21 + 268 at max_len = 2^39.  With one slice
  * per row the workgroup writes the result itself; otherwise it writes ws[row][slice] and a second
  * launch, one thread per row, adds the row's slices in index order.  No read-modify-write on
@@ -22,44 +21,14 @@
  * gaps are never loaded into a store.
  */
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_mix_hip.h"
+#define DANET_EXT mix
+#define DANET_EXT_UPPER MIX
+#include "ext_core.h"
+#include "ragged_rows.h"
+#include "sumsq_f64.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-static thread_local char g_err[256] = "";
-
-static void mix_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_mix_last_error(void) { return g_err; }
-extern "C" int danet_mix_abi_version(void) { return DANET_MIX_ABI_VERSION; }
-
-#define MIX_CHECK_ARG(cond, ...)   \
-  do {                             \
-    if (!(cond)) {                 \
-      mix_set_error(__VA_ARGS__);  \
-      return DANET_MIX_ERR_ARG;    \
-    }                              \
-  } while (0)
-
-#define MIX_CHECK_LAUNCH()                                                                          \
-  do {                                                                                              \
-    const hipError_t e_ = hipGetLastError();                                                        \
-    if (e_ != hipSuccess) {                                                                         \
-      mix_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return DANET_MIX_ERR_LAUNCH;                                                                  \
-    }                                                                                               \
-  } while (0)
-
-static const int kThreads = 256;
-static const int kWaves = kThreads / 64;
 static const int64_t kMinSlice = 65536;
 static const int kMaxSlices = 256;
 static const int64_t kMaxLen = (int64_t)1 << 39;
@@ -81,42 +50,20 @@ static Slicing slicing_of(int64_t max_len) {
 
 extern "C" size_t danet_mix_workspace_bytes(int n_utt, int64_t max_len) {
   if (n_utt < 1 || max_len < 0 || max_len > kMaxLen) {
-    mix_set_error("workspace_bytes: need n_utt >= 1 and 0 <= max_len <= 2^39 (got %d, %lld)", n_utt,
-                  (long long)max_len);
+    set_error("workspace_bytes: need n_utt >= 1 and 0 <= max_len <= 2^39 (got %d, %lld)", n_utt,
+              (long long)max_len);
     return (size_t)-1;
   }
   const Slicing g = slicing_of(max_len);
   return g.n_slices == 1 ? 0 : (size_t)n_utt * (size_t)g.n_slices * sizeof(double);
 }
 
-struct PowerArgs {
-  const float* pool;
-  int64_t pool_len;
-  const int64_t* offsets;
-  const int64_t* lengths;
-  int64_t max_len;
+struct PowerArgs : RowTable {
   int64_t slice;
   int n_slices;
   double* out;
   double* ws;      /* [n_utt][n_slices] when n_slices > 1 */
 };
-
-/* the row is clamped, never trusted: -> [off, off + len) inside the pool, 0 <= len <= max_len */
-__device__ __forceinline__ void clamp_row(const PowerArgs& a, int u, int64_t& off, int64_t& len) {
-  off = a.offsets[u];
-  len = a.lengths[u];
-  if (len < 0) len = 0;
-  if (off < 0) {
-    len = (off <= -len) ? 0 : len + off;      /* the part in front of the pool is cut off */
-    off = 0;
-  }
-  if (off > a.pool_len) off = a.pool_len;
-  if (len > a.pool_len - off) len = a.pool_len - off;
-  if (len > a.max_len) len = a.max_len;
-}
-
-__device__ __forceinline__ double sq(float x) { return (double)x * (double)x; }
-__device__ __forceinline__ double sq4(f32x4 v) { return (sq(v[0]) + sq(v[1])) + (sq(v[2]) + sq(v[3])); }
 
 __global__ __launch_bounds__(kThreads) void mix_power_kernel(PowerArgs a) {
   __shared__ double part[kWaves];
@@ -132,29 +79,9 @@ __global__ __launch_bounds__(kThreads) void mix_power_kernel(PowerArgs a) {
   }
   const int64_t n = min(a.slice, len - b);
   const float* x = a.pool + off + b;
-  const int64_t head = min(n, (int64_t)((4 - (int)(((uintptr_t)x >> 2) & 3)) & 3));
-  const int64_t nvec = (n - head) >> 2;
-  const int64_t tail = n - head - 4 * nvec;
-  const f32x4* xv = reinterpret_cast<const f32x4*>(x + head);
-
-  double acc = 0.0;
-  int64_t i = tid;
-  for (; i + 3 * kThreads < nvec; i += 4 * kThreads) {
-    const f32x4 v0 = xv[i], v1 = xv[i + kThreads], v2 = xv[i + 2 * kThreads], v3 = xv[i + 3 * kThreads];
-    acc += sq4(v0);
-    acc += sq4(v1);
-    acc += sq4(v2);
-    acc += sq4(v3);
-  }
-  for (; i < nvec; i += kThreads) acc += sq4(xv[i]);
-  if (tid < head) acc += sq(x[tid]);
-  if (tid < tail) acc += sq(x[head + 4 * nvec + tid]);
-
-  for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m, 64);     /* every lane: the wave's sum */
-  if ((tid & 63) == 0) part[tid >> 6] = acc;
-  __syncthreads();
+  wave_sums(slice_sumsq(x, n), part);
   if (tid == 0) {
-    const double r = (part[0] + part[1]) + (part[2] + part[3]);
+    const double r = four_waves(part);
     if (a.n_slices == 1) a.out[u] = r;
     else a.ws[(int64_t)u * a.n_slices + s] = r;
   }
@@ -175,28 +102,28 @@ __global__ __launch_bounds__(kThreads) void mix_power_rows_kernel(PowerArgs a, i
 extern "C" int danet_mix_power(void* stream, int n_utt, const float* pool, int64_t pool_len,
                                const int64_t* offsets, const int64_t* lengths, int64_t max_len, double* out_f64,
                                void* ws, size_t ws_bytes) {
-  MIX_CHECK_ARG(n_utt >= 1, "power: n_utt must be >= 1 (got %d)", n_utt);
-  MIX_CHECK_ARG(pool_len >= 0, "power: pool_len must be >= 0");
-  MIX_CHECK_ARG(max_len >= 0 && max_len <= kMaxLen, "power: max_len must be in [0, 2^39] (got %lld)",
-                (long long)max_len);
-  MIX_CHECK_ARG(pool && offsets && lengths && out_f64, "power: null pointer");
-  MIX_CHECK_ARG(((uintptr_t)pool & 3) == 0 && ((uintptr_t)offsets & 7) == 0 && ((uintptr_t)lengths & 7) == 0 &&
-                    ((uintptr_t)out_f64 & 7) == 0 && ((uintptr_t)ws & 7) == 0,
-                "power: misaligned pointer (pool 4-byte; offsets, lengths, out, ws 8-byte)");
+  CHECK_ARG(n_utt >= 1, "power: n_utt must be >= 1 (got %d)", n_utt);
+  CHECK_ARG(pool_len >= 0, "power: pool_len must be >= 0");
+  CHECK_ARG(max_len >= 0 && max_len <= kMaxLen, "power: max_len must be in [0, 2^39] (got %lld)",
+            (long long)max_len);
+  CHECK_ARG(pool && offsets && lengths && out_f64, "power: null pointer");
+  CHECK_ARG(((uintptr_t)pool & 3) == 0 && ((uintptr_t)offsets & 7) == 0 && ((uintptr_t)lengths & 7) == 0 &&
+                ((uintptr_t)out_f64 & 7) == 0 && ((uintptr_t)ws & 7) == 0,
+            "power: misaligned pointer (pool 4-byte; offsets, lengths, out, ws 8-byte)");
   const Slicing g = slicing_of(max_len);
-  MIX_CHECK_ARG((int64_t)n_utt * g.n_slices < ((int64_t)1 << 31), "power: n_utt * slices per row must be < 2^31");
+  CHECK_ARG((int64_t)n_utt * g.n_slices < ((int64_t)1 << 31), "power: n_utt * slices per row must be < 2^31");
   const size_t need = danet_mix_workspace_bytes(n_utt, max_len);
-  MIX_CHECK_ARG(need == 0 || ws != nullptr, "power: null pointer (ws, %zu bytes needed)", need);
-  MIX_CHECK_ARG(ws_bytes >= need, "power: workspace too small (%zu < %zu)", ws_bytes, need);
+  CHECK_ARG(need == 0 || ws != nullptr, "power: null pointer (ws, %zu bytes needed)", need);
+  CHECK_ARG(ws_bytes >= need, "power: workspace too small (%zu < %zu)", ws_bytes, need);
   PowerArgs a;
   a.pool = pool; a.pool_len = pool_len; a.offsets = offsets; a.lengths = lengths; a.max_len = max_len;
   a.slice = g.slice; a.n_slices = g.n_slices; a.out = out_f64; a.ws = (double*)ws;
   mix_power_kernel<<<dim3((unsigned)((int64_t)n_utt * g.n_slices)), kThreads, 0, (hipStream_t)stream>>>(a);
-  MIX_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   if (g.n_slices > 1) {
     mix_power_rows_kernel<<<dim3((unsigned)((n_utt + kThreads - 1) / kThreads)), kThreads, 0,
                             (hipStream_t)stream>>>(a, n_utt);
-    MIX_CHECK_LAUNCH();
+    CHECK_LAUNCH();
   }
   return DANET_MIX_OK;
 }
@@ -246,22 +173,22 @@ __global__ __launch_bounds__(kThreads) void mix_scale_kernel(ScaleArgs a) {
 
 extern "C" int danet_mix_scale_c64(void* stream, int n_utt, int t_count, int F, float* buf_c64, int64_t ld,
                                    const float* gains) {
-  MIX_CHECK_ARG(n_utt >= 1 && t_count >= 1 && F >= 1, "scale_c64: n_utt, t_count and F must be >= 1 (got %d, %d, %d)",
-                n_utt, t_count, F);
-  MIX_CHECK_ARG(buf_c64 && gains, "scale_c64: null pointer");
-  MIX_CHECK_ARG(ld >= F, "scale_c64: ld must be >= F (%lld < %d)", (long long)ld, F);
-  MIX_CHECK_ARG(ld < ((int64_t)1 << 40), "scale_c64: ld too large");
-  MIX_CHECK_ARG(((uintptr_t)buf_c64 & 7) == 0 && ((uintptr_t)gains & 3) == 0,
-                "scale_c64: misaligned pointer (buf 8-byte, gains 4-byte)");
+  CHECK_ARG(n_utt >= 1 && t_count >= 1 && F >= 1, "scale_c64: n_utt, t_count and F must be >= 1 (got %d, %d, %d)",
+            n_utt, t_count, F);
+  CHECK_ARG(buf_c64 && gains, "scale_c64: null pointer");
+  CHECK_ARG(ld >= F, "scale_c64: ld must be >= F (%lld < %d)", (long long)ld, F);
+  CHECK_ARG(ld < ((int64_t)1 << 40), "scale_c64: ld too large");
+  CHECK_ARG(((uintptr_t)buf_c64 & 7) == 0 && ((uintptr_t)gains & 3) == 0,
+            "scale_c64: misaligned pointer (buf 8-byte, gains 4-byte)");
   ScaleArgs a;
   a.buf = (float2*)buf_c64; a.gains = gains; a.ld = ld; a.t_count = t_count; a.F = F;
   a.dense = (ld == F) ? 1 : 0;
   a.span = (int64_t)t_count * F;
   a.rows = F >= kPiece ? 1 : kPiece / F;
   const int64_t n_chunks = a.dense ? (a.span + kPiece - 1) / kPiece : ((int64_t)t_count + a.rows - 1) / a.rows;
-  MIX_CHECK_ARG(n_chunks * n_utt < ((int64_t)1 << 31), "scale_c64: n_utt * workgroups per utterance must be < 2^31");
+  CHECK_ARG(n_chunks * n_utt < ((int64_t)1 << 31), "scale_c64: n_utt * workgroups per utterance must be < 2^31");
   a.n_chunks = (int)n_chunks;
   mix_scale_kernel<<<dim3((unsigned)(n_chunks * n_utt)), kThreads, 0, (hipStream_t)stream>>>(a);
-  MIX_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_MIX_OK;
 }

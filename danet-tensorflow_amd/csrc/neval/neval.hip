@@ -15,40 +15,12 @@
  * is the third output per utterance.
  */
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_neval_hip.h"
+#define DANET_EXT neval
+#define DANET_EXT_UPPER NEVAL
+#include "ext_core.h"
 #include "wave_metric.h"
-
-static thread_local char g_err[256] = "";
-
-static void neval_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_neval_last_error(void) { return g_err; }
-extern "C" int danet_neval_abi_version(void) { return DANET_NEVAL_ABI_VERSION; }
-
-#define NEVAL_CHECK_ARG(cond, ...)   \
-  do {                               \
-    if (!(cond)) {                   \
-      neval_set_error(__VA_ARGS__);  \
-      return DANET_NEVAL_ERR_ARG;    \
-    }                                \
-  } while (0)
-
-#define NEVAL_CHECK_LAUNCH()                                                                          \
-  do {                                                                                                \
-    const hipError_t e_ = hipGetLastError();                                                          \
-    if (e_ != hipSuccess) {                                                                           \
-      neval_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return DANET_NEVAL_ERR_LAUNCH;                                                                  \
-    }                                                                                                 \
-  } while (0)
 
 static_assert(kMaxC == DANET_NEVAL_MAX_C, "csrc/wave_metric.h and include/danet_neval_hip.h disagree");
 static const int kMaxM = 2 * DANET_NEVAL_MAX_C + 1;
@@ -89,8 +61,8 @@ __global__ __launch_bounds__(kThreads) void neval_synth_kernel(NevalSynthArgs a)
 
 extern "C" size_t danet_neval_workspace_bytes(int B, int C, int T, int N, int S) {
   if (!synth_shape_ok(B, C, T, N, S) || C > kMaxC) {
-    neval_set_error("workspace_bytes: need B >= 1, 1 <= C <= %d, T >= 2, N a power of two in 64..1024 and "
-                    "N/8 <= S <= N/2 (got %d, %d, %d, %d, %d)", kMaxC, B, C, T, N, S);
+    set_error("workspace_bytes: need B >= 1, 1 <= C <= %d, T >= 2, N a power of two in 64..1024 and "
+              "N/8 <= S <= N/2 (got %d, %d, %d, %d, %d)", kMaxC, B, C, T, N, S);
     return (size_t)-1;
   }
   const size_t Ls = (size_t)(T - 1) * (size_t)S, M = 2 * (size_t)C + 1;
@@ -102,23 +74,23 @@ extern "C" size_t danet_neval_workspace_bytes(int B, int C, int T, int N, int S)
 extern "C" int danet_neval_synth(void* stream, int B, int C, int T, int N, int S, const float* ref_c64,
                                  const float* est_c64, const float* noise_c64, const float* noise_gain,
                                  const float* window, float* wav) {
-  NEVAL_CHECK_ARG(B >= 1 && C >= 1, "synth: B and C must be >= 1 (got %d, %d)", B, C);
-  NEVAL_CHECK_ARG(T >= 2, "synth: T must be >= 2 (got %d)", T);
-  NEVAL_CHECK_ARG(N >= 64 && N <= 1024 && (N & (N - 1)) == 0, "synth: N must be a power of two in 64..1024 (got %d)",
-                  N);
-  NEVAL_CHECK_ARG(S >= 1 && 2 * (int64_t)S <= N && 8 * (int64_t)S >= N, "synth: S must be in [N/8, N/2] (got %d at N = %d)",
-                  S, N);
-  NEVAL_CHECK_ARG(ref_c64 && est_c64 && noise_c64 && window && wav, "synth: null pointer");
-  NEVAL_CHECK_ARG(((uintptr_t)ref_c64 & 7) == 0 && ((uintptr_t)est_c64 & 7) == 0 && ((uintptr_t)noise_c64 & 7) == 0 &&
-                      ((uintptr_t)noise_gain & 3) == 0 && ((uintptr_t)window & 3) == 0 && ((uintptr_t)wav & 3) == 0,
-                  "synth: misaligned pointer (ref, est, noise 8-byte; noise_gain, window, wav 4-byte)");
-  NEVAL_CHECK_ARG((int64_t)(T - 1) * S < ((int64_t)1 << 31), "synth: (T - 1) * S must be < 2^31");
+  CHECK_ARG(B >= 1 && C >= 1, "synth: B and C must be >= 1 (got %d, %d)", B, C);
+  CHECK_ARG(T >= 2, "synth: T must be >= 2 (got %d)", T);
+  CHECK_ARG(N >= 64 && N <= 1024 && (N & (N - 1)) == 0, "synth: N must be a power of two in 64..1024 (got %d)",
+            N);
+  CHECK_ARG(S >= 1 && 2 * (int64_t)S <= N && 8 * (int64_t)S >= N, "synth: S must be in [N/8, N/2] (got %d at N = %d)",
+            S, N);
+  CHECK_ARG(ref_c64 && est_c64 && noise_c64 && window && wav, "synth: null pointer");
+  CHECK_ARG(((uintptr_t)ref_c64 & 7) == 0 && ((uintptr_t)est_c64 & 7) == 0 && ((uintptr_t)noise_c64 & 7) == 0 &&
+                ((uintptr_t)noise_gain & 3) == 0 && ((uintptr_t)window & 3) == 0 && ((uintptr_t)wav & 3) == 0,
+            "synth: misaligned pointer (ref, est, noise 8-byte; noise_gain, window, wav 4-byte)");
+  CHECK_ARG((int64_t)(T - 1) * S < ((int64_t)1 << 31), "synth: (T - 1) * S must be < 2^31");
   const NevalSynthArgs a = {(const float2*)ref_c64, (const float2*)est_c64, (const float2*)noise_c64, noise_gain,
                             synth_args(C, T, N, S, window, wav)};
   const int64_t blocks = (int64_t)B * (2 * (int64_t)C + 1) * a.s.tiles;
-  NEVAL_CHECK_ARG(blocks < ((int64_t)1 << 31), "synth: B * (2C + 1) * tiles must be < 2^31");
+  CHECK_ARG(blocks < ((int64_t)1 << 31), "synth: B * (2C + 1) * tiles must be < 2^31");
   neval_synth_kernel<<<dim3((unsigned)blocks), kThreads, synth_lds_bytes(a.s), (hipStream_t)stream>>>(a);
-  NEVAL_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_NEVAL_OK;
 }
 
@@ -131,15 +103,15 @@ __global__ __launch_bounds__(kThreads) void neval_gram_kernel(int M, int n_pairs
 }
 
 extern "C" int danet_neval_gram(void* stream, int B, int M, int64_t Ls, const float* wav, double* G) {
-  NEVAL_CHECK_ARG(B >= 1, "gram: B must be >= 1 (got %d)", B);
-  NEVAL_CHECK_ARG(M >= 1 && M <= kMaxM, "gram: M must be in 1..%d (got %d)", kMaxM, M);
-  NEVAL_CHECK_ARG(Ls >= 1 && Ls < ((int64_t)1 << 31), "gram: Ls must be in [1, 2^31) (got %lld)", (long long)Ls);
-  NEVAL_CHECK_ARG(wav && G, "gram: null pointer");
-  NEVAL_CHECK_ARG(((uintptr_t)wav & 3) == 0 && ((uintptr_t)G & 7) == 0, "gram: misaligned pointer (wav 4-byte, G 8-byte)");
+  CHECK_ARG(B >= 1, "gram: B must be >= 1 (got %d)", B);
+  CHECK_ARG(M >= 1 && M <= kMaxM, "gram: M must be in 1..%d (got %d)", kMaxM, M);
+  CHECK_ARG(Ls >= 1 && Ls < ((int64_t)1 << 31), "gram: Ls must be in [1, 2^31) (got %lld)", (long long)Ls);
+  CHECK_ARG(wav && G, "gram: null pointer");
+  CHECK_ARG(((uintptr_t)wav & 3) == 0 && ((uintptr_t)G & 7) == 0, "gram: misaligned pointer (wav 4-byte, G 8-byte)");
   const int n_pairs = M * (M + 1) / 2;
-  NEVAL_CHECK_ARG((int64_t)B * n_pairs < ((int64_t)1 << 31), "gram: B * M * (M + 1) / 2 must be < 2^31");
+  CHECK_ARG((int64_t)B * n_pairs < ((int64_t)1 << 31), "gram: B * M * (M + 1) / 2 must be < 2^31");
   neval_gram_kernel<<<dim3((unsigned)((int64_t)B * n_pairs)), kThreads, 0, (hipStream_t)stream>>>(M, n_pairs, Ls, wav, G);
-  NEVAL_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_NEVAL_OK;
 }
 
@@ -201,13 +173,13 @@ __global__ __launch_bounds__(kThreads) void neval_si_sdr_kernel(int B, int C, co
 
 extern "C" int danet_neval_si_sdr(void* stream, int B, int C, const double* G, double* per_utt, int32_t* perm_idx,
                                   double* mean3) {
-  NEVAL_CHECK_ARG(B >= 1, "si_sdr: B must be >= 1 (got %d)", B);
-  NEVAL_CHECK_ARG(C >= 1 && C <= kMaxC, "si_sdr: C must be in 1..%d (got %d)", kMaxC, C);
-  NEVAL_CHECK_ARG(G && per_utt && perm_idx && mean3, "si_sdr: null pointer");
-  NEVAL_CHECK_ARG(((uintptr_t)G & 7) == 0 && ((uintptr_t)per_utt & 7) == 0 && ((uintptr_t)mean3 & 7) == 0 &&
-                      ((uintptr_t)perm_idx & 3) == 0,
-                  "si_sdr: misaligned pointer (G, per_utt, mean3 8-byte; perm_idx 4-byte)");
+  CHECK_ARG(B >= 1, "si_sdr: B must be >= 1 (got %d)", B);
+  CHECK_ARG(C >= 1 && C <= kMaxC, "si_sdr: C must be in 1..%d (got %d)", kMaxC, C);
+  CHECK_ARG(G && per_utt && perm_idx && mean3, "si_sdr: null pointer");
+  CHECK_ARG(((uintptr_t)G & 7) == 0 && ((uintptr_t)per_utt & 7) == 0 && ((uintptr_t)mean3 & 7) == 0 &&
+                ((uintptr_t)perm_idx & 3) == 0,
+            "si_sdr: misaligned pointer (G, per_utt, mean3 8-byte; perm_idx 4-byte)");
   neval_si_sdr_kernel<<<dim3(1), kThreads, 0, (hipStream_t)stream>>>(B, C, G, per_utt, perm_idx, mean3);
-  NEVAL_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_NEVAL_OK;
 }

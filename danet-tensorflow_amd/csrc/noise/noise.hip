@@ -14,41 +14,14 @@
  * Contraction is OFF for this file: fl(g * n) is rounded before it is added, as the header promises.
  */
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_noise_hip.h"
+#define DANET_EXT noise
+#define DANET_EXT_UPPER NOISE
+#include "ext_core.h"
 
 #pragma clang fp contract(off)
 
-static thread_local char g_err[256] = "";
-
-static void noise_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_noise_last_error(void) { return g_err; }
-extern "C" int danet_noise_abi_version(void) { return DANET_NOISE_ABI_VERSION; }
-
-#define NOISE_CHECK_ARG(cond, ...)   \
-  do {                               \
-    if (!(cond)) {                   \
-      noise_set_error(__VA_ARGS__);  \
-      return DANET_NOISE_ERR_ARG;    \
-    }                                \
-  } while (0)
-
-#define NOISE_CHECK_LAUNCH()                                                                          \
-  do {                                                                                                \
-    const hipError_t e_ = hipGetLastError();                                                          \
-    if (e_ != hipSuccess) {                                                                           \
-      noise_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return DANET_NOISE_ERR_LAUNCH;                                                                  \
-    }                                                                                                 \
-  } while (0)
 
 static const int kThreads = 64;          /* one wave per workgroup */
 static const int64_t kMaxN = (int64_t)1 << 40;
@@ -111,18 +84,18 @@ static void launch(dim3 grid, hipStream_t stream, const NoiseArgs& a) {
 extern "C" int danet_noise_frontend_fwd(void* stream, int B, int C, int64_t N, const float* src_c64,
                                         const float* noise_c64, const float* gain, float* mix_pwr, float* mix_log,
                                         float* phasor, float* src_pwr, float* mix_c64) {
-  NOISE_CHECK_ARG(B >= 1, "frontend_fwd: B must be >= 1 (got %d)", B);
-  NOISE_CHECK_ARG(C >= 1 && C <= DANET_NOISE_MAX_C, "frontend_fwd: C must be in [1, %d] (got %d)", DANET_NOISE_MAX_C,
-                  C);
-  NOISE_CHECK_ARG(N >= 1 && N < kMaxN, "frontend_fwd: N must be in [1, 2^40) (got %lld)", (long long)N);
-  NOISE_CHECK_ARG((int64_t)B * C <= kMaxTotal / N, "frontend_fwd: B * C * N must be < 2^58");
-  NOISE_CHECK_ARG(src_c64 && noise_c64 && mix_pwr && mix_log && phasor && src_pwr,
-                  "frontend_fwd: null pointer (src, noise, mix_pwr, mix_log, phasor and src_pwr are required)");
-  NOISE_CHECK_ARG(((uintptr_t)src_c64 & 7) == 0 && ((uintptr_t)noise_c64 & 7) == 0 && ((uintptr_t)phasor & 7) == 0 &&
-                      ((uintptr_t)mix_c64 & 7) == 0 && ((uintptr_t)gain & 3) == 0 && ((uintptr_t)mix_pwr & 3) == 0 &&
-                      ((uintptr_t)mix_log & 3) == 0 && ((uintptr_t)src_pwr & 3) == 0,
-                  "frontend_fwd: misaligned pointer (src, noise, phasor, mix_c64 8-byte; gain, mix_pwr, mix_log, "
-                  "src_pwr 4-byte)");
+  CHECK_ARG(B >= 1, "frontend_fwd: B must be >= 1 (got %d)", B);
+  CHECK_ARG(C >= 1 && C <= DANET_NOISE_MAX_C, "frontend_fwd: C must be in [1, %d] (got %d)", DANET_NOISE_MAX_C,
+            C);
+  CHECK_ARG(N >= 1 && N < kMaxN, "frontend_fwd: N must be in [1, 2^40) (got %lld)", (long long)N);
+  CHECK_ARG((int64_t)B * C <= kMaxTotal / N, "frontend_fwd: B * C * N must be < 2^58");
+  CHECK_ARG(src_c64 && noise_c64 && mix_pwr && mix_log && phasor && src_pwr,
+            "frontend_fwd: null pointer (src, noise, mix_pwr, mix_log, phasor and src_pwr are required)");
+  CHECK_ARG(((uintptr_t)src_c64 & 7) == 0 && ((uintptr_t)noise_c64 & 7) == 0 && ((uintptr_t)phasor & 7) == 0 &&
+                ((uintptr_t)mix_c64 & 7) == 0 && ((uintptr_t)gain & 3) == 0 && ((uintptr_t)mix_pwr & 3) == 0 &&
+                ((uintptr_t)mix_log & 3) == 0 && ((uintptr_t)src_pwr & 3) == 0,
+            "frontend_fwd: misaligned pointer (src, noise, phasor, mix_c64 8-byte; gain, mix_pwr, mix_log, "
+            "src_pwr 4-byte)");
   NoiseArgs a;
   a.src = (const float2*)src_c64; a.noise = (const float2*)noise_c64; a.gain = gain;
   a.mix_pwr = mix_pwr; a.mix_log = mix_log; a.phasor = (float2*)phasor; a.src_pwr = src_pwr;
@@ -141,6 +114,6 @@ extern "C" int danet_noise_frontend_fwd(void* stream, int B, int C, int64_t N, c
     case 7: launch<7>(grid, s, a); break;
     default: launch<8>(grid, s, a); break;
   }
-  NOISE_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_NOISE_OK;
 }

@@ -6,6 +6,7 @@
 // the complex spectra are read as interleaved (re,im) float2.
 #include "common.h"
 #include "options.h"
+#include "adam_one.h"
 #include <atomic>
 
 // ------------------------------------------------------------------ front-end
@@ -443,15 +444,6 @@ extern "C" int danet_leaky_relu(danet_stream_t stream, int64_t n, const float* x
 // clip like tf.clip_by_value (fminf/fmaxf alone would turn it into -clip).  zero_grad: the
 // gradient is overwritten with 0 after use, so the next step's backward can accumulate into
 // it without a separate fill kernel.
-__device__ __forceinline__ void adam_one(float& th, float& gi, float& mi, float& vi, float lr_t,
-                                         float b1, float b2, float eps, float clip, float gscale) {
-  float g = gi * gscale;
-  if (clip > 0.f) g = (g != g) ? g : fminf(fmaxf(g, -clip), clip);   // main.py:359-362
-  mi = b1 * mi + (1.f - b1) * g;
-  vi = b2 * vi + (1.f - b2) * g * g;
-  th -= lr_t * mi / (sqrtf(vi) + eps);                              // eps outside the root (TF1)
-}
-
 __global__ __launch_bounds__(256) void adam_clip_kernel(
     int64_t n, float* __restrict__ theta, float* __restrict__ grad, float* __restrict__ m,
     float* __restrict__ v, float lr_t, float b1, float b2, float eps, float clip, float gscale,

@@ -24,41 +24,11 @@
  * No atomics, no host round trip, plain HIP C++.
  */
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_prep_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-static thread_local char g_err[256] = "";
-
-static void prep_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_prep_last_error(void) { return g_err; }
-extern "C" int danet_prep_abi_version(void) { return DANET_PREP_ABI_VERSION; }
-
-#define PREP_CHECK_ARG(cond, ...)   \
-  do {                              \
-    if (!(cond)) {                  \
-      prep_set_error(__VA_ARGS__);  \
-      return DANET_PREP_ERR_ARG;    \
-    }                               \
-  } while (0)
-
-#define PREP_CHECK_LAUNCH()                                                                          \
-  do {                                                                                               \
-    const hipError_t e_ = hipGetLastError();                                                         \
-    if (e_ != hipSuccess) {                                                                          \
-      prep_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return DANET_PREP_ERR_LAUNCH;                                                                  \
-    }                                                                                                \
-  } while (0)
+#define DANET_EXT prep
+#define DANET_EXT_UPPER PREP
+#include "ext_core.h"
 
 static const int kThreads = 256;
 
@@ -81,12 +51,12 @@ __host__ __device__ __forceinline__ int64_t frames_of(int64_t Ls, int N, int S) 
 
 extern "C" int danet_prep_num_frames(int64_t Ls, int N, int S) {
   if (N <= 0 || S <= 0 || S > N || Ls < N) {
-    prep_set_error("num_frames: need 0 < S <= N <= Ls (Ls=%lld, N=%d, S=%d)", (long long)Ls, N, S);
+    set_error("num_frames: need 0 < S <= N <= Ls (Ls=%lld, N=%d, S=%d)", (long long)Ls, N, S);
     return DANET_PREP_ERR_ARG;
   }
   const int64_t T = frames_of(Ls, N, S);
   if (T > 0x7fffffff) {
-    prep_set_error("num_frames: frame count does not fit an int");
+    set_error("num_frames: frame count does not fit an int");
     return DANET_PREP_ERR_ARG;
   }
   return (int)T;
@@ -95,7 +65,7 @@ extern "C" int danet_prep_num_frames(int64_t Ls, int N, int S) {
 /* plan layout: float2 tw[N/2] | float scale | pad to 16 bytes */
 extern "C" size_t danet_prep_workspace_bytes(int N) {
   if (!valid_fft_size(N)) {
-    prep_set_error("workspace_bytes: N must be a power of two in [64, 4096] (got %d)", N);
+    set_error("workspace_bytes: N must be a power of two in [64, 4096] (got %d)", N);
     return (size_t)-1;
   }
   return (size_t)N * 4 + 16;
@@ -124,16 +94,16 @@ __global__ __launch_bounds__(kThreads) void prep_plan_kernel(int N, const float*
 
 extern "C" int danet_prep_stft_plan(void* stream, int N, const float* window, void* plan_ws,
                                     size_t plan_bytes) {
-  PREP_CHECK_ARG(valid_fft_size(N), "stft_plan: N must be a power of two in [64, 4096] (got %d)", N);
-  PREP_CHECK_ARG(window != nullptr && plan_ws != nullptr, "stft_plan: null pointer");
-  PREP_CHECK_ARG(((uintptr_t)window & 3) == 0 && ((uintptr_t)plan_ws & 15) == 0,
-                 "stft_plan: window must be 4-byte and plan_ws 16-byte aligned");
-  PREP_CHECK_ARG(plan_bytes >= danet_prep_workspace_bytes(N), "stft_plan: workspace too small (%zu < %zu)",
-                 plan_bytes, danet_prep_workspace_bytes(N));
+  CHECK_ARG(valid_fft_size(N), "stft_plan: N must be a power of two in [64, 4096] (got %d)", N);
+  CHECK_ARG(window != nullptr && plan_ws != nullptr, "stft_plan: null pointer");
+  CHECK_ARG(((uintptr_t)window & 3) == 0 && ((uintptr_t)plan_ws & 15) == 0,
+            "stft_plan: window must be 4-byte and plan_ws 16-byte aligned");
+  CHECK_ARG(plan_bytes >= danet_prep_workspace_bytes(N), "stft_plan: workspace too small (%zu < %zu)",
+            plan_bytes, danet_prep_workspace_bytes(N));
   float2* tw = (float2*)plan_ws;
   float* scale = (float*)((char*)plan_ws + (size_t)N * 4);
   prep_plan_kernel<<<1, kThreads, 0, (hipStream_t)stream>>>(N, window, tw, scale);
-  PREP_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_PREP_OK;
 }
 
@@ -325,24 +295,24 @@ extern "C" int danet_prep_stft_batch(void* stream, int n_utt, const float* pool,
                                      const danet_prep_utt_t* desc, int T_out, int t_begin, int t_count, int N,
                                      int S, const float* window, const void* plan_ws, float* out_c64,
                                      int64_t ld_out) {
-  PREP_CHECK_ARG(valid_fft_size(N), "stft_batch: N must be a power of two in [64, 4096] (got %d)", N);
-  PREP_CHECK_ARG(S > 0 && S <= N, "stft_batch: stride must be in (0, N] (got %d)", S);
-  PREP_CHECK_ARG(n_utt >= 1, "stft_batch: n_utt must be >= 1 (got %d)", n_utt);
-  PREP_CHECK_ARG(pool && desc && window && plan_ws && out_c64, "stft_batch: null pointer");
-  PREP_CHECK_ARG(pool_len >= 0, "stft_batch: pool_len must be >= 0");
-  PREP_CHECK_ARG(T_out >= 1 && t_begin >= 0 && t_count >= 1 && (int64_t)t_begin + t_count <= T_out,
-                 "stft_batch: need 0 <= t_begin, 1 <= t_count, t_begin + t_count <= T_out (got %d, %d, %d)",
-                 t_begin, t_count, T_out);
+  CHECK_ARG(valid_fft_size(N), "stft_batch: N must be a power of two in [64, 4096] (got %d)", N);
+  CHECK_ARG(S > 0 && S <= N, "stft_batch: stride must be in (0, N] (got %d)", S);
+  CHECK_ARG(n_utt >= 1, "stft_batch: n_utt must be >= 1 (got %d)", n_utt);
+  CHECK_ARG(pool && desc && window && plan_ws && out_c64, "stft_batch: null pointer");
+  CHECK_ARG(pool_len >= 0, "stft_batch: pool_len must be >= 0");
+  CHECK_ARG(T_out >= 1 && t_begin >= 0 && t_count >= 1 && (int64_t)t_begin + t_count <= T_out,
+            "stft_batch: need 0 <= t_begin, 1 <= t_count, t_begin + t_count <= T_out (got %d, %d, %d)",
+            t_begin, t_count, T_out);
   const int F = N / 2 + 1;
-  PREP_CHECK_ARG(ld_out >= F, "stft_batch: ld_out must be >= F (%lld < %d)", (long long)ld_out, F);
-  PREP_CHECK_ARG(ld_out < ((int64_t)1 << 40), "stft_batch: ld_out too large");
-  PREP_CHECK_ARG(((uintptr_t)pool & 3) == 0 && ((uintptr_t)window & 3) == 0 && ((uintptr_t)desc & 7) == 0 &&
-                     ((uintptr_t)out_c64 & 7) == 0 && ((uintptr_t)plan_ws & 15) == 0,
-                 "stft_batch: misaligned pointer (pool, window 4-byte; desc, out 8-byte; plan_ws 16-byte)");
+  CHECK_ARG(ld_out >= F, "stft_batch: ld_out must be >= F (%lld < %d)", (long long)ld_out, F);
+  CHECK_ARG(ld_out < ((int64_t)1 << 40), "stft_batch: ld_out too large");
+  CHECK_ARG(((uintptr_t)pool & 3) == 0 && ((uintptr_t)window & 3) == 0 && ((uintptr_t)desc & 7) == 0 &&
+                ((uintptr_t)out_c64 & 7) == 0 && ((uintptr_t)plan_ws & 15) == 0,
+            "stft_batch: misaligned pointer (pool, window 4-byte; desc, out 8-byte; plan_ws 16-byte)");
   const int fpw = frames_per_workgroup(N);
   const int64_t n_chunks = ((int64_t)t_count + fpw - 1) / fpw;
-  PREP_CHECK_ARG(n_chunks * n_utt < ((int64_t)1 << 31), "stft_batch: n_utt * ceil(t_count / %d) must be < 2^31",
-                 fpw);
+  CHECK_ARG(n_chunks * n_utt < ((int64_t)1 << 31), "stft_batch: n_utt * ceil(t_count / %d) must be < 2^31",
+            fpw);
   PrepArgs a;
   a.pool = pool; a.pool_len = pool_len; a.desc = desc; a.window = window;
   a.tw = (const float2*)plan_ws;
@@ -357,7 +327,7 @@ extern "C" int danet_prep_stft_batch(void* stream, int n_utt, const float* pool,
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) {
       (void)hipGetLastError();
-      prep_set_error("stft_batch: no HIP device");
+      set_error("stft_batch: no HIP device");
       return DANET_PREP_ERR_LAUNCH;
     }
     if (dev != lds_dev) {
@@ -365,13 +335,13 @@ extern "C" int danet_prep_stft_batch(void* stream, int n_utt, const float* pool,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
       if (e != hipSuccess) {
         (void)hipGetLastError();
-        prep_set_error("stft_batch: cannot reserve %zu bytes of LDS: %s", kMaxLds, hipGetErrorString(e));
+        set_error("stft_batch: cannot reserve %zu bytes of LDS: %s", kMaxLds, hipGetErrorString(e));
         return DANET_PREP_ERR_LAUNCH;
       }
       lds_dev = dev;
     }
   }
   prep_stft_batch_kernel<<<dim3((unsigned)(n_chunks * n_utt)), kThreads, lds, (hipStream_t)stream>>>(a);
-  PREP_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_PREP_OK;
 }

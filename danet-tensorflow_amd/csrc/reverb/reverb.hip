@@ -19,39 +19,19 @@
  * across the chunks.  Everything written goes through ordinary vector stores.
  */
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_reverb_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-static thread_local char g_err[256] = "";
-
-static void reverb_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_reverb_last_error(void) { return g_err; }
-extern "C" int danet_reverb_abi_version(void) { return DANET_REVERB_ABI_VERSION; }
-
-#define REVERB_CHECK_ARG(cond, ...)   \
-  do {                                \
-    if (!(cond)) {                    \
-      reverb_set_error(__VA_ARGS__);  \
-      return DANET_REVERB_ERR_ARG;    \
-    }                                 \
-  } while (0)
+#define DANET_EXT reverb
+#define DANET_EXT_UPPER REVERB
+#include "ext_core.h"
+#include "ragged_rows.h"
 
 static const int kThreads = 128;
 static const int kPerLane = 8;                    /* consecutive outputs of a lane           */
 static const int kTile = kThreads * kPerLane;     /* outputs of a block                      */
 static const int kChunk = 1024;                   /* taps staged at a time                   */
 static const int kBlocksPerCu = 4;
-static const int64_t kMaxLen = (int64_t)1 << 40;
+static const int64_t kMaxLen = kMaxSpan;          /* 2^40: what cut_span cuts to */
 
 static_assert(kTile == 1024, "the header's rule names the block of 1024 outputs");
 static_assert(kChunk % 4 == 0 && kTile % 4 == 0 && DANET_REVERB_MAX_TAPS % 4 == 0, "16-byte vectors");
@@ -85,13 +65,10 @@ __device__ __forceinline__ Row load_row(const ReverbArgs& a, int u) {
   if (L < 0) L = 0;
   if (L > kMaxLen) L = kMaxLen;
   r.L = L;
-  /* [0, L) cut to the samples i with 0 <= so + i < src_len */
-  r.lo = 0;
-  r.hi = 0;
-  if (r.so < a.src_len && r.so > -L) {              /* so > -L >= -2^40: no overflow below */
-    r.lo = r.so < 0 ? -r.so : 0;
-    r.hi = L < a.src_len - r.so ? L : a.src_len - r.so;
-  }
+  int64_t lo, hi;                                   /* [0, L) cut to the samples i with 0 <= so + i < src_len */
+  cut_span(r.so, L, a.src_len, lo, hi);
+  r.lo = lo;
+  r.hi = hi;
   /* the span [out_begin, out_begin + out_count) cut to [0, L) ... */
   int64_t ob = d.out_begin, oc = d.out_count;
   if (oc < 0) oc = 0;
@@ -211,20 +188,20 @@ static int compute_units(void) {
 extern "C" int danet_reverb_apply(void* stream, int n_utt, const float* src, int64_t src_len,
                                   const danet_reverb_utt_t* desc, const float* bank, int n_taps, float* dst,
                                   int64_t dst_len) {
-  REVERB_CHECK_ARG(n_utt >= 1, "apply: n_utt must be >= 1 (got %d)", n_utt);
-  REVERB_CHECK_ARG(src && desc && bank && dst, "apply: null pointer");
-  REVERB_CHECK_ARG(n_taps >= DANET_REVERB_MIN_TAPS && n_taps <= DANET_REVERB_MAX_TAPS && n_taps % 4 == 0,
-                   "apply: n_taps must be a multiple of 4 in [%d, %d] (got %d)", DANET_REVERB_MIN_TAPS,
-                   DANET_REVERB_MAX_TAPS, n_taps);
-  REVERB_CHECK_ARG(src_len >= 0 && src_len <= kMaxLen && dst_len >= 0 && dst_len <= kMaxLen,
-                   "apply: src_len and dst_len must be in [0, 2^40] (got %lld, %lld)", (long long)src_len,
-                   (long long)dst_len);
-  REVERB_CHECK_ARG(((uintptr_t)src & 3) == 0 && ((uintptr_t)dst & 3) == 0 && ((uintptr_t)desc & 7) == 0 &&
-                       ((uintptr_t)bank & 15) == 0,
-                   "apply: misaligned pointer (src, dst 4-byte; desc 8-byte; bank 16-byte)");
+  CHECK_ARG(n_utt >= 1, "apply: n_utt must be >= 1 (got %d)", n_utt);
+  CHECK_ARG(src && desc && bank && dst, "apply: null pointer");
+  CHECK_ARG(n_taps >= DANET_REVERB_MIN_TAPS && n_taps <= DANET_REVERB_MAX_TAPS && n_taps % 4 == 0,
+            "apply: n_taps must be a multiple of 4 in [%d, %d] (got %d)", DANET_REVERB_MIN_TAPS,
+            DANET_REVERB_MAX_TAPS, n_taps);
+  CHECK_ARG(src_len >= 0 && src_len <= kMaxLen && dst_len >= 0 && dst_len <= kMaxLen,
+            "apply: src_len and dst_len must be in [0, 2^40] (got %lld, %lld)", (long long)src_len,
+            (long long)dst_len);
+  CHECK_ARG(((uintptr_t)src & 3) == 0 && ((uintptr_t)dst & 3) == 0 && ((uintptr_t)desc & 7) == 0 &&
+                ((uintptr_t)bank & 15) == 0,
+            "apply: misaligned pointer (src, dst 4-byte; desc 8-byte; bank 16-byte)");
   const int cus = compute_units();
   if (cus < 1) {
-    reverb_set_error("apply: no device (%s:%d)", __FILE__, __LINE__);
+    set_error("apply: no device (%s:%d)", __FILE__, __LINE__);
     return DANET_REVERB_ERR_LAUNCH;
   }
   /* a row's span of c outputs inside dst meets at most c / 1024 + 2 blocks: with disjoint spans this bounds
@@ -235,10 +212,6 @@ extern "C" int danet_reverb_apply(void* stream, int n_utt, const float* src, int
   a.src = src; a.src_len = src_len; a.desc = desc; a.bank = bank; a.dst = dst; a.dst_len = dst_len;
   a.n_utt = n_utt; a.n_taps = n_taps;
   reverb_apply_kernel<<<dim3((unsigned)(bound < most ? bound : most)), kThreads, 0, (hipStream_t)stream>>>(a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    reverb_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-    return DANET_REVERB_ERR_LAUNCH;
-  }
+  CHECK_LAUNCH();
   return DANET_REVERB_OK;
 }

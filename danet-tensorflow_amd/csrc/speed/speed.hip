@@ -19,32 +19,12 @@
  * store neighbouring outputs.  Each output is one chain of 32 fused multiply-adds, j ascending, from +0.
  */
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_speed_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-static thread_local char g_err[256] = "";
-
-static void speed_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_speed_last_error(void) { return g_err; }
-extern "C" int danet_speed_abi_version(void) { return DANET_SPEED_ABI_VERSION; }
-
-#define SPEED_CHECK_ARG(cond, ...)   \
-  do {                               \
-    if (!(cond)) {                   \
-      speed_set_error(__VA_ARGS__);  \
-      return DANET_SPEED_ERR_ARG;    \
-    }                                \
-  } while (0)
+#define DANET_EXT speed
+#define DANET_EXT_UPPER SPEED
+#include "ext_core.h"
+#include "ragged_rows.h"
 
 static const int kQ = DANET_SPEED_PHASES;
 static const int kQShift = 9;
@@ -56,7 +36,7 @@ static const int kPitch = kTaps + 4;          /* floats per table row in LDS    
 /* floats of a staged span: 1023 * 640 / 512 rounded up + 32 taps, + 3 in front (alignment) and up to the
  * next multiple of 4 behind */
 static const int kSpan = 1320;
-static const int64_t kMaxLen = (int64_t)1 << 40;
+static const int64_t kMaxLen = kMaxSpan;      /* 2^40: what cut_span cuts to */
 
 static_assert((1 << kQShift) == kQ, "Q is 2^kQShift");
 static_assert(((kTile - 1) * DANET_SPEED_P_MAX + kQ - 1) / kQ + kTaps + 3 + 3 <= kSpan, "staged span");
@@ -64,8 +44,8 @@ static_assert(kTile == 2 * kThreads && kQ * kTaps / 4 == 8 * kThreads, "tile and
 
 extern "C" int64_t danet_speed_out_len(int64_t L, int p) {
   if (L < 1 || L > kMaxLen || p < DANET_SPEED_P_MIN || p > DANET_SPEED_P_MAX) {
-    speed_set_error("out_len: need 1 <= L <= 2^40 and %d <= p <= %d (got %lld, %d)", DANET_SPEED_P_MIN,
-                    DANET_SPEED_P_MAX, (long long)L, p);
+    set_error("out_len: need 1 <= L <= 2^40 and %d <= p <= %d (got %lld, %d)", DANET_SPEED_P_MIN,
+              DANET_SPEED_P_MAX, (long long)L, p);
     return -1;
   }
   return (L - 1) * kQ / p + 1;
@@ -87,17 +67,6 @@ struct Row {
   int64_t so, lo, hi, dof, nlo, nhi;
   int p;
 };
-
-/* [0, len) cut to the indices i with 0 <= off + i < total -> [lo, hi), empty as lo = hi = 0 */
-__device__ __forceinline__ void cut_span(int64_t off, int64_t len, int64_t total, int64_t& lo, int64_t& hi) {
-  if (len < 0) len = 0;
-  if (len > kMaxLen) len = kMaxLen;
-  lo = 0;
-  hi = 0;
-  if (off >= total || off <= -len) return;      /* entirely behind or in front of the buffer */
-  lo = off < 0 ? -off : 0;                      /* off > -len >= -2^40: no overflow          */
-  hi = len < total - off ? len : total - off;   /* off < total <= 2^40                       */
-}
 
 __device__ __forceinline__ Row load_row(const SpeedArgs& a, int u) {
   const danet_speed_utt_t d = a.desc[u];
@@ -185,17 +154,17 @@ static int compute_units(void) {
 extern "C" int danet_speed_resample(void* stream, int n_utt, const float* src_pool, int64_t src_len,
                                     const danet_speed_utt_t* desc, const float* table, float* dst,
                                     int64_t dst_len) {
-  SPEED_CHECK_ARG(n_utt >= 1, "resample: n_utt must be >= 1 (got %d)", n_utt);
-  SPEED_CHECK_ARG(src_pool && desc && table && dst, "resample: null pointer");
-  SPEED_CHECK_ARG(src_len >= 0 && src_len <= kMaxLen && dst_len >= 0 && dst_len <= kMaxLen,
-                  "resample: src_len and dst_len must be in [0, 2^40] (got %lld, %lld)", (long long)src_len,
-                  (long long)dst_len);
-  SPEED_CHECK_ARG(((uintptr_t)src_pool & 3) == 0 && ((uintptr_t)dst & 3) == 0 && ((uintptr_t)desc & 7) == 0 &&
-                      ((uintptr_t)table & 15) == 0,
-                  "resample: misaligned pointer (src_pool, dst 4-byte; desc 8-byte; table 16-byte)");
+  CHECK_ARG(n_utt >= 1, "resample: n_utt must be >= 1 (got %d)", n_utt);
+  CHECK_ARG(src_pool && desc && table && dst, "resample: null pointer");
+  CHECK_ARG(src_len >= 0 && src_len <= kMaxLen && dst_len >= 0 && dst_len <= kMaxLen,
+            "resample: src_len and dst_len must be in [0, 2^40] (got %lld, %lld)", (long long)src_len,
+            (long long)dst_len);
+  CHECK_ARG(((uintptr_t)src_pool & 3) == 0 && ((uintptr_t)dst & 3) == 0 && ((uintptr_t)desc & 7) == 0 &&
+                ((uintptr_t)table & 15) == 0,
+            "resample: misaligned pointer (src_pool, dst 4-byte; desc 8-byte; table 16-byte)");
   const int cus = compute_units();
   if (cus < 1) {
-    speed_set_error("resample: no device (%s:%d)", __FILE__, __LINE__);
+    set_error("resample: no device (%s:%d)", __FILE__, __LINE__);
     return DANET_SPEED_ERR_LAUNCH;
   }
   /* no row has more than ceil(its span inside dst / 1024) tiles: with disjoint spans this bounds the sum */
@@ -204,10 +173,6 @@ extern "C" int danet_speed_resample(void* stream, int n_utt, const float* src_po
   a.src = src_pool; a.src_len = src_len; a.desc = desc; a.table = table; a.dst = dst; a.dst_len = dst_len;
   a.n_utt = n_utt;
   speed_resample_kernel<<<dim3((unsigned)(bound < cus ? bound : cus)), kThreads, 0, (hipStream_t)stream>>>(a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    speed_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-    return DANET_SPEED_ERR_LAUNCH;
-  }
+  CHECK_LAUNCH();
   return DANET_SPEED_OK;
 }

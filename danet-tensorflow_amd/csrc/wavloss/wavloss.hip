@@ -17,40 +17,12 @@
  *           bins 0 and N/2 are Re Z[0] +- Im Z[0]; scaled by dloss c_k / N and written (through the phasor or not).
  */
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "danet_wavloss_hip.h"
+#define DANET_EXT wavloss
+#define DANET_EXT_UPPER WAVLOSS
+#include "ext_core.h"
 #include "wave_metric.h"
-
-static thread_local char g_err[256] = "";
-
-static void wavloss_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-extern "C" const char* danet_wavloss_last_error(void) { return g_err; }
-extern "C" int danet_wavloss_abi_version(void) { return DANET_WAVLOSS_ABI_VERSION; }
-
-#define WAVLOSS_CHECK_ARG(cond, ...)   \
-  do {                                 \
-    if (!(cond)) {                     \
-      wavloss_set_error(__VA_ARGS__);  \
-      return DANET_WAVLOSS_ERR_ARG;    \
-    }                                  \
-  } while (0)
-
-#define WAVLOSS_CHECK_LAUNCH()                                                                          \
-  do {                                                                                                  \
-    const hipError_t e_ = hipGetLastError();                                                            \
-    if (e_ != hipSuccess) {                                                                             \
-      wavloss_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return DANET_WAVLOSS_ERR_LAUNCH;                                                                  \
-    }                                                                                                   \
-  } while (0)
 
 static_assert(kMaxC == DANET_WAVLOSS_MAX_C, "csrc/wave_metric.h and include/danet_wavloss_hip.h disagree");
 
@@ -121,17 +93,17 @@ __global__ __launch_bounds__(kThreads) void wavloss_fwd_kernel(int B, int C, con
 
 extern "C" int danet_wavloss_fwd(void* stream, int B, int C, const double* G, double* loss_f64, float* loss_f32,
                                  double* per_utt, int32_t* perm_idx, int32_t* pair, double* coef) {
-  WAVLOSS_CHECK_ARG(B >= 1, "fwd: B must be >= 1 (got %d)", B);
-  WAVLOSS_CHECK_ARG(C >= 1 && C <= kMaxC, "fwd: C must be in 1..%d (got %d)", kMaxC, C);
-  WAVLOSS_CHECK_ARG((int64_t)B * 4 * C * C < ((int64_t)1 << 31), "fwd: B * 4 C^2 must be < 2^31");
-  WAVLOSS_CHECK_ARG(G && loss_f64 && loss_f32 && per_utt && perm_idx && pair && coef, "fwd: null pointer");
-  WAVLOSS_CHECK_ARG(((uintptr_t)G & 7) == 0 && ((uintptr_t)loss_f64 & 7) == 0 && ((uintptr_t)per_utt & 7) == 0 &&
-                        ((uintptr_t)coef & 7) == 0 && ((uintptr_t)loss_f32 & 3) == 0 &&
-                        ((uintptr_t)perm_idx & 3) == 0 && ((uintptr_t)pair & 3) == 0,
-                    "fwd: misaligned pointer (G, loss_f64, per_utt, coef 8-byte; loss_f32, perm_idx, pair 4-byte)");
+  CHECK_ARG(B >= 1, "fwd: B must be >= 1 (got %d)", B);
+  CHECK_ARG(C >= 1 && C <= kMaxC, "fwd: C must be in 1..%d (got %d)", kMaxC, C);
+  CHECK_ARG((int64_t)B * 4 * C * C < ((int64_t)1 << 31), "fwd: B * 4 C^2 must be < 2^31");
+  CHECK_ARG(G && loss_f64 && loss_f32 && per_utt && perm_idx && pair && coef, "fwd: null pointer");
+  CHECK_ARG(((uintptr_t)G & 7) == 0 && ((uintptr_t)loss_f64 & 7) == 0 && ((uintptr_t)per_utt & 7) == 0 &&
+                ((uintptr_t)coef & 7) == 0 && ((uintptr_t)loss_f32 & 3) == 0 &&
+                ((uintptr_t)perm_idx & 3) == 0 && ((uintptr_t)pair & 3) == 0,
+            "fwd: misaligned pointer (G, loss_f64, per_utt, coef 8-byte; loss_f32, perm_idx, pair 4-byte)");
   wavloss_fwd_kernel<<<dim3(1), kThreads, 0, (hipStream_t)stream>>>(B, C, G, loss_f64, loss_f32, per_utt, perm_idx,
                                                                     pair, coef);
-  WAVLOSS_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_WAVLOSS_OK;
 }
 
@@ -256,24 +228,24 @@ __global__ __launch_bounds__(kThreads) void wavloss_bwd_kernel(BwdArgs a) {
 extern "C" int danet_wavloss_bwd(void* stream, int B, int C, int T, int N, int S, const float* wav,
                                  const int32_t* pair, const double* coef, const float* window, const float* dloss,
                                  const float* phasor, float* out) {
-  WAVLOSS_CHECK_ARG(B >= 1, "bwd: B must be >= 1 (got %d)", B);
-  WAVLOSS_CHECK_ARG(C >= 1 && C <= kMaxC, "bwd: C must be in 1..%d (got %d)", kMaxC, C);
-  WAVLOSS_CHECK_ARG(T >= 2, "bwd: T must be >= 2 (got %d)", T);
-  WAVLOSS_CHECK_ARG(N >= 64 && N <= 1024 && (N & (N - 1)) == 0, "bwd: N must be a power of two in 64..1024 (got %d)", N);
-  WAVLOSS_CHECK_ARG(S >= 1 && 2 * (int64_t)S <= N && 8 * (int64_t)S >= N, "bwd: S must be in [N/8, N/2] (got %d at N = %d)",
-                    S, N);
-  WAVLOSS_CHECK_ARG(wav && pair && coef && window && out, "bwd: null pointer");
-  WAVLOSS_CHECK_ARG(((uintptr_t)wav & 3) == 0 && ((uintptr_t)pair & 3) == 0 && ((uintptr_t)window & 3) == 0 &&
-                        ((uintptr_t)dloss & 3) == 0 && ((uintptr_t)coef & 7) == 0 && ((uintptr_t)phasor & 7) == 0 &&
-                        ((uintptr_t)out & (phasor ? 3 : 7)) == 0,
-                    "bwd: misaligned pointer (wav, pair, window, dloss 4-byte; coef, phasor 8-byte; out 8-byte in the "
-                    "complex form, 4-byte in the real one)");
-  WAVLOSS_CHECK_ARG((int64_t)(T - 1) * S < ((int64_t)1 << 31), "bwd: (T - 1) * S must be < 2^31");
-  WAVLOSS_CHECK_ARG((int64_t)T * (N / 2 + 1) < ((int64_t)1 << 31), "bwd: T * F must be < 2^31");
+  CHECK_ARG(B >= 1, "bwd: B must be >= 1 (got %d)", B);
+  CHECK_ARG(C >= 1 && C <= kMaxC, "bwd: C must be in 1..%d (got %d)", kMaxC, C);
+  CHECK_ARG(T >= 2, "bwd: T must be >= 2 (got %d)", T);
+  CHECK_ARG(N >= 64 && N <= 1024 && (N & (N - 1)) == 0, "bwd: N must be a power of two in 64..1024 (got %d)", N);
+  CHECK_ARG(S >= 1 && 2 * (int64_t)S <= N && 8 * (int64_t)S >= N, "bwd: S must be in [N/8, N/2] (got %d at N = %d)",
+            S, N);
+  CHECK_ARG(wav && pair && coef && window && out, "bwd: null pointer");
+  CHECK_ARG(((uintptr_t)wav & 3) == 0 && ((uintptr_t)pair & 3) == 0 && ((uintptr_t)window & 3) == 0 &&
+                ((uintptr_t)dloss & 3) == 0 && ((uintptr_t)coef & 7) == 0 && ((uintptr_t)phasor & 7) == 0 &&
+                ((uintptr_t)out & (phasor ? 3 : 7)) == 0,
+            "bwd: misaligned pointer (wav, pair, window, dloss 4-byte; coef, phasor 8-byte; out 8-byte in the "
+            "complex form, 4-byte in the real one)");
+  CHECK_ARG((int64_t)(T - 1) * S < ((int64_t)1 << 31), "bwd: (T - 1) * S must be < 2^31");
+  CHECK_ARG((int64_t)T * (N / 2 + 1) < ((int64_t)1 << 31), "bwd: T * F must be < 2^31");
   const int frames = DANET_WAVLOSS_TILE_FRAMES(N);
   const int tiles = (T + frames - 1) / frames;
   const int64_t blocks = (int64_t)B * C * tiles;
-  WAVLOSS_CHECK_ARG(blocks < ((int64_t)1 << 31), "bwd: B * C * tiles must be < 2^31");
+  CHECK_ARG(blocks < ((int64_t)1 << 31), "bwd: B * C * tiles must be < 2^31");
   BwdArgs a;
   a.wav = wav; a.pair = pair; a.coef = coef; a.window = window; a.dloss = dloss;
   a.phasor = (const float2*)phasor; a.out = out;
@@ -283,6 +255,6 @@ extern "C" int danet_wavloss_bwd(void* stream, int B, int C, int T, int N, int S
   /* twiddles N + frames * N + span (frames - 1) * S + N floats: <= 3N/2 (1 + frames) <= 16384 at S = N/2 */
   const size_t lds_bytes = ((size_t)N + (size_t)frames * N + (size_t)(frames - 1) * S + N) * sizeof(float);
   wavloss_bwd_kernel<<<dim3((unsigned)blocks), kThreads, lds_bytes, (hipStream_t)stream>>>(a);
-  WAVLOSS_CHECK_LAUNCH();
+  CHECK_LAUNCH();
   return DANET_WAVLOSS_OK;
 }

@@ -420,6 +420,62 @@ _prep_plans = {}         # (device index, N, window bytes) -> plan tensor
 _prep_plans_fast = {}    # (device index, N, window data_ptr, window version) -> (window, plan)
 
 
+def _desc_table(who, dtype_name, desc, validate, device):
+    '''the descriptor table of `who` -> (device tensor, rows): a record array of the dtype named `dtype_name` goes
+    through validate(desc) and is uploaded; a device tensor of rows of that size is the caller's to have validated'''
+    dtype = globals()[dtype_name]
+    if not torch.is_tensor(desc):
+        desc = np.asarray(desc)
+        if desc.dtype != dtype:
+            raise TypeError('%s: desc must be a %s record array or a device tensor' % (who, dtype_name))
+        validate(desc)
+        desc = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8).copy()).to(device)
+    row = dtype.itemsize
+    assert desc.is_cuda and desc.is_contiguous() and (desc.numel() * desc.element_size()) % row == 0
+    return desc, desc.numel() * desc.element_size() // row
+
+
+def _c64_row_pitch(t, F):
+    '''the row pitch, in complex elements, of a complex64 [n_utt, t_count, >= F] view whose last dimension is
+    contiguous and whose utterances lie t_count rows apart'''
+    n_utt, t_count = t.shape[:2]
+    ld = t.stride(1) if t_count > 1 else max(t.stride(1), F)
+    assert t.stride(2) == 1 and (n_utt == 1 or t.stride(0) == t_count * ld), t.stride()
+    return ld
+
+
+def _row_tables(who, pool, offsets, lengths, max_len):
+    '''the (offsets, lengths, max_len) of the rows of `pool` as `who` launches them: host sequences are validated
+    (a row outside the pool is a ValueError) and uploaded, max_len taken from them when not given; device tensors
+    are the caller's to have validated and need max_len'''
+    if not torch.is_tensor(offsets):
+        offsets, lengths = np.asarray(offsets, dtype=np.int64), np.asarray(lengths, dtype=np.int64)
+        if offsets.shape != lengths.shape or offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError('%s: offsets and lengths must be two vectors of one length >= 1' % who)
+        _check_source_spans(who, offsets, lengths, pool.numel(), 0)
+        if max_len is None:
+            max_len = int(lengths.max())
+        offsets, lengths = torch.from_numpy(offsets).to(pool.device), torch.from_numpy(lengths).to(pool.device)
+    if max_len is None:
+        raise ValueError('%s: device tables need max_len' % who)
+    return offsets, lengths, max_len
+
+
+def _check_source_spans(who, so, sl, src_len, min_len=1):
+    '''ValueError naming the first row [so, so + sl) that is shorter than min_len or outside a pool of src_len'''
+    bad = np.nonzero((so < 0) | (sl < min_len) | (so + sl > src_len))[0]
+    if len(bad):
+        u = int(bad[0])
+        raise ValueError('%s: utterance %d [%d, %d) is outside the pool of %d samples'
+                         % (who, u, so[u], so[u] + sl[u], src_len))
+
+
+def _spans_apart(lo, hi):
+    '''no two of the spans [lo, hi) share a sample'''
+    order = np.argsort(lo, kind='stable')
+    return not np.any(lo[order][1:] < hi[order][:-1])
+
+
 def prep_num_frames(n_samples, fft_size, fft_stride):
     '''frames of an n_samples waveform (danet_prep_num_frames); ValueError when it is shorter than the window'''
     T = _lib.load_prep().danet_prep_num_frames(int(n_samples), fft_size, fft_stride)
@@ -457,9 +513,7 @@ def _prep_plan(window, fft_size):
     plan = _prep_plans.get(key)
     if plan is None:
         L = _lib.load_prep()
-        nbytes = L.danet_prep_workspace_bytes(fft_size)
-        if nbytes == ctypes.c_size_t(-1).value:
-            _lib.prep_check(-1)
+        nbytes = _lib.bytes_or_raise(L.danet_prep_workspace_bytes(fft_size), _lib.prep_check)
         plan = torch.zeros(nbytes, dtype=torch.uint8, device=window.device)
         _lib.prep_check(L.danet_prep_stft_plan(_lib.stream(), fft_size, ptr(window), ptr(plan), nbytes))
         _prep_plans[key] = plan
@@ -482,19 +536,12 @@ def stft_batch(pool, desc, T_out, window, fft_size, fft_stride, t_begin=0, t_cou
     if t_count is None:
         t_count = T_out - t_begin
     F = fft_size // 2 + 1
-    if not torch.is_tensor(desc):
-        desc = np.asarray(desc)
-        if desc.dtype != PREP_DESC_DTYPE:
-            raise TypeError('stft_batch: desc must be a PREP_DESC_DTYPE record array or a device tensor')
-        prep_desc(desc['offset'], desc['length'], desc['pad_left'], T_out, pool.numel(), fft_size, fft_stride)
-        desc = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8).copy()).to(pool.device)
-    assert desc.is_cuda and desc.is_contiguous() and (desc.numel() * desc.element_size()) % 24 == 0
-    n_utt = desc.numel() * desc.element_size() // 24
+    desc, n_utt = _desc_table('stft_batch', 'PREP_DESC_DTYPE', desc, lambda d: prep_desc(
+        d['offset'], d['length'], d['pad_left'], T_out, pool.numel(), fft_size, fft_stride), pool.device)
     if out is None:
         out = torch.empty(n_utt, t_count, F, dtype=torch.complex64, device=pool.device)
     assert out.dtype == torch.complex64 and out.is_cuda and tuple(out.shape) == (n_utt, t_count, F), out.shape
-    ld = out.stride(1) if t_count > 1 else max(out.stride(1), F)
-    assert out.stride(2) == 1 and (n_utt == 1 or out.stride(0) == t_count * ld), out.stride()
+    ld = _c64_row_pitch(out, F)
     plan = _prep_plan(window, fft_size)
     with _lib.timed('stft_batch'):
         _lib.prep_check(_lib.load_prep().danet_prep_stft_batch(
@@ -513,28 +560,13 @@ def mix_power(pool, offsets, lengths, max_len=None):
     before any upload or launch) or int64 device tensors the caller has validated (the kernel clamps,
     and `max_len`, an upper bound of the lengths, must then be given).'''
     assert pool.is_cuda and pool.dtype == torch.float32 and pool.dim() == 1 and pool.is_contiguous()
-    if not torch.is_tensor(offsets):
-        offsets, lengths = np.asarray(offsets, dtype=np.int64), np.asarray(lengths, dtype=np.int64)
-        if offsets.shape != lengths.shape or offsets.ndim != 1 or len(offsets) < 1:
-            raise ValueError('mix_power: offsets and lengths must be two vectors of one length >= 1')
-        bad = np.nonzero((offsets < 0) | (lengths < 0) | (offsets + lengths > pool.numel()))[0]
-        if len(bad):
-            u = int(bad[0])
-            raise ValueError('mix_power: utterance %d [%d, %d) is outside the pool of %d samples'
-                             % (u, offsets[u], offsets[u] + lengths[u], pool.numel()))
-        if max_len is None:
-            max_len = int(lengths.max())
-        offsets, lengths = torch.from_numpy(offsets).to(pool.device), torch.from_numpy(lengths).to(pool.device)
-    if max_len is None:
-        raise ValueError('mix_power: device tables need max_len')
+    offsets, lengths, max_len = _row_tables('mix_power', pool, offsets, lengths, max_len)
     for t in (offsets, lengths):
         assert t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous()
     n = offsets.numel()
     assert lengths.numel() == n
     L = _lib.load_mix()
-    nbytes = L.danet_mix_workspace_bytes(n, int(max_len))
-    if nbytes == ctypes.c_size_t(-1).value:
-        _lib.mix_check(-1)
+    nbytes = _lib.bytes_or_raise(L.danet_mix_workspace_bytes(n, int(max_len)), _lib.mix_check)
     ws = _lib.workspace(nbytes, pool.device, 'mix') if nbytes else None
     out = torch.empty(n, dtype=torch.float64, device=pool.device)
     with _lib.timed('mix_power'):
@@ -551,8 +583,7 @@ def mix_scale_(batch, gains):
     n_utt, t_count, F = batch.shape
     assert gains.is_cuda and gains.dtype == torch.float32 and gains.dim() == 1 and gains.is_contiguous()
     assert gains.numel() == n_utt and gains.device == batch.device
-    ld = batch.stride(1) if t_count > 1 else max(batch.stride(1), F)
-    assert batch.stride(2) == 1 and (n_utt == 1 or batch.stride(0) == t_count * ld), batch.stride()
+    ld = _c64_row_pitch(batch, F)
     with _lib.timed('mix_scale'):
         _lib.mix_check(_lib.load_mix().danet_mix_scale_c64(
             _lib.stream(), n_utt, t_count, F, ptr(torch.view_as_real(batch)), ld, ptr(gains)))
@@ -580,20 +611,7 @@ def level_activity(pool, offsets, lengths, thresholds, g, hang, max_len=None):
         raise ValueError('level_activity: g must be inside (0, 1), got %r' % (g,))
     if not 0 <= hang <= LEVEL_MAX_HANG:
         raise ValueError('level_activity: hang must be in [0, 2^40] samples, got %r' % (hang,))
-    if not torch.is_tensor(offsets):
-        offsets, lengths = np.asarray(offsets, dtype=np.int64), np.asarray(lengths, dtype=np.int64)
-        if offsets.shape != lengths.shape or offsets.ndim != 1 or len(offsets) < 1:
-            raise ValueError('level_activity: offsets and lengths must be two vectors of one length >= 1')
-        bad = np.nonzero((offsets < 0) | (lengths < 0) | (offsets + lengths > pool.numel()))[0]
-        if len(bad):
-            u = int(bad[0])
-            raise ValueError('level_activity: utterance %d [%d, %d) is outside the pool of %d samples'
-                             % (u, offsets[u], offsets[u] + lengths[u], pool.numel()))
-        if max_len is None:
-            max_len = int(lengths.max())
-        offsets, lengths = torch.from_numpy(offsets).to(pool.device), torch.from_numpy(lengths).to(pool.device)
-    if max_len is None:
-        raise ValueError('level_activity: device tables need max_len')
+    offsets, lengths, max_len = _row_tables('level_activity', pool, offsets, lengths, max_len)
     max_len = int(max_len)
     for t in (offsets, lengths):
         assert t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous()
@@ -611,9 +629,7 @@ def level_activity(pool, offsets, lengths, thresholds, g, hang, max_len=None):
         raise ValueError('level_activity: need 0 <= max_len <= 2^31 and rows * tiles per row < 2^31 (got max_len %d, '
                          '%d rows)' % (max_len, n))
     L = _lib.load_level()
-    nbytes = L.danet_level_workspace_bytes(n, max_len)
-    if nbytes == ctypes.c_size_t(-1).value:
-        _lib.level_check(-1)
+    nbytes = _lib.bytes_or_raise(L.danet_level_workspace_bytes(n, max_len), _lib.level_check)
     # once per pool and as large as a fifth of it: a buffer of the call's own, not the grow-only scratch
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=pool.device)
     out = torch.empty(n, LEVEL_THRESHOLDS, dtype=torch.int64, device=pool.device)
@@ -664,18 +680,13 @@ def speed_desc(src_offsets, src_lengths, dst_offsets, dst_lengths, p, src_len, d
     d['src_offset'], d['src_length'], d['dst_offset'], d['dst_length'] = src_offsets, src_lengths, dst_offsets, dst_lengths
     d['p'], d['reserved'] = p, 0
     so, sl, do, dl, pp = (d[k].astype(np.int64) for k in ('src_offset', 'src_length', 'dst_offset', 'dst_length', 'p'))
-    bad = np.nonzero((so < 0) | (sl < 1) | (so + sl > src_len))[0]
-    if len(bad):
-        u = int(bad[0])
-        raise ValueError('speed_resample: utterance %d [%d, %d) is outside the pool of %d samples'
-                         % (u, so[u], so[u] + sl[u], src_len))
+    _check_source_spans('speed_resample', so, sl, src_len)
     bad = np.nonzero((pp < SPEED_P_MIN) | (pp > SPEED_P_MAX))[0]
     if len(bad):
         raise ValueError('speed_resample: utterance %d: p = %d is outside [%d, %d]'
                          % (bad[0], pp[bad[0]], SPEED_P_MIN, SPEED_P_MAX))
-    order = np.argsort(do, kind='stable')
     bad = np.nonzero((do < 0) | (dl < 0) | (do + dl > dst_len))[0]
-    if len(bad) or np.any(do[order][1:] < (do + dl)[order][:-1]):
+    if len(bad) or not _spans_apart(do, do + dl):
         raise ValueError('speed_resample: the destination spans must lie inside the buffer of %d samples and '
                          'apart from each other' % dst_len)
     return d
@@ -691,16 +702,9 @@ def speed_resample(pool, desc, table, out):
         assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()
     assert table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()
     assert tuple(table.shape) == (SPEED_PHASES, SPEED_TAPS) and table.device == pool.device == out.device
-    if not torch.is_tensor(desc):
-        desc = np.asarray(desc)
-        if desc.dtype != SPEED_DESC_DTYPE:
-            raise TypeError('speed_resample: desc must be a SPEED_DESC_DTYPE record array or a device tensor')
-        speed_desc(desc['src_offset'], desc['src_length'], desc['dst_offset'], desc['dst_length'], desc['p'],
-                   pool.numel(), out.numel())
-        desc = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8).copy()).to(pool.device)
-    row = SPEED_DESC_DTYPE.itemsize
-    assert desc.is_cuda and desc.is_contiguous() and (desc.numel() * desc.element_size()) % row == 0
-    n_utt = desc.numel() * desc.element_size() // row
+    desc, n_utt = _desc_table('speed_resample', 'SPEED_DESC_DTYPE', desc, lambda d: speed_desc(
+        d['src_offset'], d['src_length'], d['dst_offset'], d['dst_length'], d['p'], pool.numel(), out.numel()),
+        pool.device)
     with _lib.timed('speed_resample'):
         _lib.speed_check(_lib.load_speed().danet_speed_resample(
             _lib.stream(), n_utt, ptr(pool), pool.numel(), ptr(desc), ptr(table), ptr(out), out.numel()))
@@ -763,11 +767,7 @@ def reverb_desc(src_offsets, src_lengths, dst_offsets, out_begin, out_count, row
     d['out_begin'], d['out_count'], d['row'], d['reserved'] = out_begin, out_count, rows, 0
     so, sl, do, ob, oc, rw = (d[k].astype(np.int64) for k in ('src_offset', 'src_length', 'dst_offset', 'out_begin',
                                                               'out_count', 'row'))
-    bad = np.nonzero((so < 0) | (sl < 1) | (so + sl > src_len))[0]
-    if len(bad):
-        u = int(bad[0])
-        raise ValueError('reverb_apply: utterance %d [%d, %d) is outside the pool of %d samples'
-                         % (u, so[u], so[u] + sl[u], src_len))
+    _check_source_spans('reverb_apply', so, sl, src_len)
     bad = np.nonzero((rw < 0) | (rw >= REVERB_ROWS))[0]
     if len(bad):
         raise ValueError('reverb_apply: utterance %d: row = %d is outside [0, %d)' % (bad[0], rw[bad[0]], REVERB_ROWS))
@@ -777,8 +777,7 @@ def reverb_desc(src_offsets, src_lengths, dst_offsets, out_begin, out_count, row
         raise ValueError('reverb_apply: utterance %d: the span [%d, %d) is outside its %d samples'
                          % (u, ob[u], ob[u] + oc[u], sl[u]))
     lo, hi = do + ob, do + ob + oc
-    order = np.argsort(lo, kind='stable')
-    if np.any(lo < 0) or np.any(hi > dst_len) or np.any(lo[order][1:] < hi[order][:-1]):
+    if np.any(lo < 0) or np.any(hi > dst_len) or not _spans_apart(lo, hi):
         raise ValueError('reverb_apply: the written spans must lie inside the buffer of %d samples and '
                          'apart from each other' % dst_len)
     return d
@@ -795,16 +794,9 @@ def reverb_apply(src, desc, bank, n_taps, out):
     assert bank.is_cuda and bank.dtype == torch.float32 and bank.is_contiguous()
     assert tuple(bank.shape) == (REVERB_ROWS, n_taps) and bank.device == src.device == out.device
     assert src.data_ptr() != out.data_ptr()
-    if not torch.is_tensor(desc):
-        desc = np.asarray(desc)
-        if desc.dtype != REVERB_DESC_DTYPE:
-            raise TypeError('reverb_apply: desc must be a REVERB_DESC_DTYPE record array or a device tensor')
-        reverb_desc(desc['src_offset'], desc['src_length'], desc['dst_offset'], desc['out_begin'], desc['out_count'],
-                    desc['row'], src.numel(), out.numel())
-        desc = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8).copy()).to(src.device)
-    row = REVERB_DESC_DTYPE.itemsize
-    assert desc.is_cuda and desc.is_contiguous() and (desc.numel() * desc.element_size()) % row == 0
-    n_utt = desc.numel() * desc.element_size() // row
+    desc, n_utt = _desc_table('reverb_apply', 'REVERB_DESC_DTYPE', desc, lambda d: reverb_desc(
+        d['src_offset'], d['src_length'], d['dst_offset'], d['out_begin'], d['out_count'], d['row'], src.numel(),
+        out.numel()), src.device)
     with _lib.timed('reverb_apply'):
         _lib.reverb_check(_lib.load_reverb().danet_reverb_apply(
             _lib.stream(), n_utt, ptr(src), src.numel(), ptr(desc), ptr(bank), int(n_taps), ptr(out), out.numel()))
@@ -845,9 +837,8 @@ def _wave_workspace(tag, cache, rows, outs, B, C, T, N, S, dev):
     hit = cache.get(key)
     if hit is not None and _lib._ws.get(key[:2] + (tag,)) is hit[0]:
         return hit
-    nbytes = getattr(getattr(_lib, 'load_' + tag)(), 'danet_%s_workspace_bytes' % tag)(B, C, T, N, S)
-    if nbytes == ctypes.c_size_t(-1).value:
-        getattr(_lib, tag + '_check')(-1)
+    nbytes = _lib.bytes_or_raise(
+        getattr(getattr(_lib, 'load_' + tag)(), 'danet_%s_workspace_bytes' % tag)(B, C, T, N, S), getattr(_lib, tag + '_check'))
     buf = _lib.workspace(nbytes, dev, tag)
     Ls = (T - 1) * S
     views, off = [], 0
@@ -1121,10 +1112,8 @@ DPCL_MAX_C = 4                                       # DANET_DPCL_MAX_C
 
 def dpcl_workspace_bytes(B, N, E, C):
     '''danet_dpcl_workspace_bytes(B, N, E, C): the bytes dpcl_stats writes and dpcl_finalize reads'''
-    n = _lib.load_dpcl().danet_dpcl_workspace_bytes(int(B), int(N), int(E), int(C))
-    if n == ctypes.c_size_t(-1).value:
-        _lib.dpcl_check(-1)
-    return n
+    return _lib.bytes_or_raise(_lib.load_dpcl().danet_dpcl_workspace_bytes(int(B), int(N), int(E), int(C)),
+                               _lib.dpcl_check)
 
 
 def _dpcl_shapes(embed, src_pwr):

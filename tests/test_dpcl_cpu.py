@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import dpcl_ref as DR
+import csrc_scan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'danet_dpcl_hip.h')
@@ -143,6 +144,8 @@ def test_dpcl_library_reads_no_environment_allocates_nothing_and_has_no_atomics(
     srcs = sorted(f for f in os.listdir(d) if f.endswith(('.hip', '.h', '.cpp')))
     assert srcs == ['dpcl.hip']
     code = re.sub(r'/\*.*?\*/', '', open(os.path.join(d, 'dpcl.hip')).read(), flags=re.S)
+    code += csrc_scan.shared_code(code)              # and the shared headers it includes, same words: the
+    assert '} while (0)' in code and '#include "ext_core.h"' in code       # allowance is for their macros
     for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new ', 'atomic', '__threadfence', 'while',
                  'common.h'):
         assert word not in code.replace('} while (0)', ''), word

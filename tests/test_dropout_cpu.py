@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import dropout_ref as D
+import csrc_scan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -104,7 +105,8 @@ def test_library_does_not_read_the_environment():
     out = subprocess.run(['nm', '-D', _lib.DROPOUT_LIB_PATH], capture_output=True, text=True, check=True)
     assert 'getenv' not in out.stdout
     src = open(os.path.join(ROOT, 'danet-tensorflow_amd', 'csrc', 'dropout', 'dropout.hip')).read()
-    assert 'getenv' not in src and 'environ' not in src
+    src += csrc_scan.shared_code(src, comments=True)
+    assert 'ext_core.h' in src and 'getenv' not in src and 'environ' not in src
 
 
 def test_core_library_abi_is_untouched():

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import gclip_ref as GR
+import csrc_scan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'danet_gclip_hip.h')
@@ -134,12 +135,17 @@ def test_gclip_library_reads_no_environment_and_allocates_nothing():
     srcs = sorted(f for f in os.listdir(d) if f.endswith(('.hip', '.h', '.cpp')))
     assert srcs == ['gclip.hip']
     code = re.sub(r'/\*.*?\*/', '', open(os.path.join(d, 'gclip.hip')).read(), flags=re.S)
+    code += csrc_scan.shared_code(code)              # and the shared headers it includes, same words: the
+    assert '} while (0)' in code and '#include "ext_core.h"' in code       # allowance is for their macros
     for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new ', 'atomic', '__threadfence', 'while'):
         assert word not in code.replace('} while (0)', ''), word
-    # adam_one is the core's, verbatim
-    core = open(os.path.join(ROOT, 'danet-tensorflow_amd', 'csrc', 'pointwise.hip')).read()
-    one = re.search(r'__device__ __forceinline__ void adam_one\(.*?\n}\n', core, flags=re.S).group(0)
-    assert one in open(os.path.join(d, 'gclip.hip')).read()
+    # adam_one is the core's: one definition, in the header both pointwise.hip and gclip.hip include
+    csrc = os.path.dirname(d)
+    one = re.compile(r'__device__ __forceinline__ void adam_one\(.*?\n}\n', flags=re.S)
+    texts = {f: open(os.path.join(csrc, f)).read() for f in ('adam_one.h', 'pointwise.hip', 'gclip/gclip.hip')}
+    assert [len(one.findall(texts[f])) for f in texts] == [1, 0, 0]
+    for f in ('pointwise.hip', 'gclip/gclip.hip'):
+        assert '#include "adam_one.h"' in texts[f] and texts[f].count('adam_one(') == 2, f
 
 
 def test_import_and_a_model_with_the_key_null_never_touch_the_library(tmp_path):

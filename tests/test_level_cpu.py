@@ -20,6 +20,7 @@ import pytest
 
 import level_ref as LR
 import noise_ref as NR
+import csrc_scan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'danet_level_hip.h')
@@ -129,6 +130,7 @@ def test_level_library_reads_no_environment_and_allocates_nothing():
     srcs = sorted(f for f in os.listdir(d) if f.endswith(('.hip', '.h', '.cpp')))
     assert srcs == ['level.hip']
     code = re.sub(r'/\*.*?\*/', '', open(os.path.join(d, 'level.hip')).read(), flags=re.S)
+    code += csrc_scan.shared_code(code)              # and the shared headers it includes, same words
     for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new ', 'atomic'):
         assert word not in code, word
 

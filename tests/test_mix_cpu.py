@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import mix_ref as M
+import csrc_scan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'danet_mix_hip.h')
@@ -93,7 +94,9 @@ def test_mix_library_reads_no_environment_and_allocates_nothing():
     d = os.path.join(ROOT, 'danet-tensorflow_amd', 'csrc', 'mix')
     srcs = [f for f in os.listdir(d) if f.endswith(('.hip', '.h', '.cpp'))]
     assert srcs == ['mix.hip']
-    for f in srcs:
+    shared = csrc_scan.shared_headers(open(os.path.join(d, 'mix.hip')).read())
+    assert [os.path.basename(p) for p in shared] == ['ext_core.h', 'ragged_rows.h', 'sumsq_f64.h']
+    for f in srcs + shared:                                                                # same words
         src = open(os.path.join(d, f)).read()
         assert 'getenv' not in src and 'environ' not in src, f
         code = re.sub(r'/\*.*?\*/', '', src, flags=re.S)

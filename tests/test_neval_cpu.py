@@ -21,6 +21,7 @@ import metric_ref as MR
 import mix_ref as M
 import neval_ref as NV
 import noise_ref as NR
+import csrc_scan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'danet_neval_hip.h')
@@ -135,8 +136,8 @@ def test_neval_library_reads_no_environment_and_allocates_nothing():
     for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new ', 'atomic'):
         assert word not in code, word
     assert 'fp contract(off)' in code                  # fl(g * z) is rounded before the split step adds it
-    shared = re.sub(r'/\*.*?\*/', '', open(os.path.join(os.path.dirname(d), 'wave_metric.h')).read(), flags=re.S)
-    assert '#include "wave_metric.h"' in code
+    shared = csrc_scan.shared_code(code)               # wave_metric.h, ext_core.h
+    assert '#include "wave_metric.h"' in code and '#include "ext_core.h"' in code
     for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new ', 'atomic'):
         assert word not in shared, word
 

@@ -21,6 +21,7 @@ import mix_ref as M
 import noise_ref as NR
 import reverb_ref as RR
 import speed_ref as SR
+import csrc_scan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'danet_noise_hip.h')
@@ -123,6 +124,7 @@ def test_noise_library_reads_no_environment_and_allocates_nothing():
     srcs = sorted(f for f in os.listdir(d) if f.endswith(('.hip', '.h', '.cpp')))
     assert srcs == ['noise.hip']
     code = re.sub(r'/\*.*?\*/', '', open(os.path.join(d, 'noise.hip')).read(), flags=re.S)
+    code += csrc_scan.shared_code(code)              # and the shared headers it includes, same words
     for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new '):
         assert word not in code, word
     assert 'fp contract(off)' in code                  # fl(g * n) is rounded before it is added

@@ -20,6 +20,7 @@ import torch
 
 import metric_ref as MR
 import wavloss_ref as WR
+import csrc_scan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'danet_wavloss_hip.h')
@@ -142,8 +143,8 @@ def test_wavloss_library_reads_no_environment_and_allocates_nothing():
     code = re.sub(r'/\*.*?\*/', '', open(os.path.join(d, 'wavloss.hip')).read(), flags=re.S)
     for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new ', 'atomic'):
         assert word not in code, word
-    shared = re.sub(r'/\*.*?\*/', '', open(os.path.join(os.path.dirname(d), 'wave_metric.h')).read(), flags=re.S)
-    assert '#include "wave_metric.h"' in code
+    shared = csrc_scan.shared_code(code)               # wave_metric.h, ext_core.h
+    assert '#include "wave_metric.h"' in code and '#include "ext_core.h"' in code
     for word in ('getenv', 'environ', 'hipMalloc', 'hipFree', 'malloc', 'new ', 'atomic'):
         assert word not in shared, word
 
