@@ -1083,6 +1083,29 @@ __device__ __forceinline__ void store_sc1_b128(__amdgpu_buffer_rsrc_t r, unsigne
 
 #define RS_NI_MAX 6
 
+// What a BPTT step does besides the hand-off, in four parts that -DRS_STEP_PATH=<sum of bits> switches for A/B
+// builds (profiles/bptt_step_path.md has each part's figure; the default is what measured fastest):
+//   1  FETCH: the owners' saved activations arrive through LDS from the waves that idle between the step's
+//      two barriers (U <= 16: the OWN threads behind the owners, one SHADOW per owner).  In the gate phase of
+//      step s a shadow hands the words it fetched a step earlier (those of step s + 1) to its owner through
+//      `act` and fetches those of step s + 2: no load is issued between a step's first exchange load and its
+//      validation, and every hand-over crosses one of the two barriers.  Off (and at U = 32, which has no
+//      idle wave): the owners load them at the step's top.
+//   2  STORE: twin 0's shadows write da of step s - 1 out of the other half of a double-buffered tile, 16
+//      bytes per thread.  OFF by default: beside FETCH it is a loss (cfg 2: 2.312 against 2.298 ms per step);
+//      the owners store their four words behind the publish.
+//   4  PRE: tanh(c), 1 - tanh^2, 1 - ig, 1 - fg, 1 - og and the bias-gradient sums of the step before are
+//      formed at the step's top, in front of the exchange, not between the barriers.
+//  32  DRAIN: a wave polls only when its own memory operations have completed (s_waitcnt vmcnt(0) in front
+//      of the exchange loads: its publish and da stores are acknowledged).  This is no wait on another
+//      workgroup; the compiler used to put the same wait in front of the owners' seven loads at the step's
+//      top, and without it the first poll leaves earlier and comes back LATE: every
+//      build without it is slower than the kernel with the seven loads in place.
+// The cell value is carried in every build: c_{t-1} of step s is c_t of step s + 1.
+#ifndef RS_STEP_PATH
+#define RS_STEP_PATH 37
+#endif
+
 template <int U, int NTW>
 __global__ __launch_bounds__(512) void lstm_bwd_rs_kernel(LstmBwdRsArgs a) {
   constexpr int NW = 8;
@@ -1091,8 +1114,15 @@ __global__ __launch_bounds__(512) void lstm_bwd_rs_kernel(LstmBwdRsArgs a) {
   constexpr int CPP = 4 * U;         // 16-byte chunks per producer
   constexpr int PPR = 512 / CPP;     // producers covered by one round of loads
   constexpr int LDA = 4 * U + 4;
+  constexpr bool SHADOW = (RS_STEP_PATH & 1) && 2 * OWN <= 512;    // the shadows fetch
+  constexpr bool SSTORE = (RS_STEP_PATH & 2) && 2 * OWN <= 512;    // the shadows store
+  constexpr bool PRE = (RS_STEP_PATH & 4) != 0;                    // dh-independent terms at the step's top
+  constexpr bool DRAIN = (RS_STEP_PATH & 32) != 0;                 // own stores acknowledged before a poll
+  constexpr int ATILE = 16 * LDA, NAT = SSTORE ? 2 : 1;
   __shared__ __attribute__((aligned(16))) float psum[PPR * OWN];  // 8 KB
-  __shared__ __attribute__((aligned(16))) float atile[16 * LDA];  // da_t own columns [row][k]
+  __shared__ __attribute__((aligned(16))) float atile[NAT * ATILE];  // da_t own columns [step & 1][row][k]
+  // the owners' words of a step: [step & 1][g | i | f | o | c of the step before in time | dy][owner]
+  __shared__ float act[SHADOW ? 2 * 6 * OWN : 4];
   // OWNSPLIT (U = 32, the wide layers): da_t as the three bf16 piece planes in the matrix instruction's
   // operand order -- [piece][row][k-block][fq][8 k of the lane], rows padded by 16 bytes.  The OWNER of a
   // (row, unit) splits its four gate values once (two split_pair) and stores twelve half-words; every
@@ -1245,6 +1275,21 @@ __global__ __launch_bounds__(512) void lstm_bwd_rs_kernel(LstmBwdRsArgs a) {
   const float* dyp = a.dy + orow0 * a.lddy + (owner ? dir * H + unit : 0);
   float* dp = a.da[dir] + orow0 * (4 * H) + ounit;
 
+  // shadow `sid` fetches for owner `sid`; for the da tile it is one 16-byte chunk of the 16 x 4U tile
+  // (row, gate, four units: H % 4 == 0 and u0 % 4 == 0, so a chunk lies inside H or outside it)
+  const int sid = tid - OWN;
+  const bool sthr = (SHADOW || SSTORE) && sid >= 0 && sid < OWN;
+  const int sbg = b0 + sid / U, sunit = u0 + sid % U;
+  const bool sfetch = SHADOW && sthr && sbg < B && sunit < H;
+  const size_t srow0 = sfetch ? ((size_t)tfirst * B + sbg) : 0;
+  const float* sgp = a.gates[dir] + srow0 * (4 * H) + (sfetch ? sunit : 0);
+  const float* scp = a.cell[dir] + srow0 * H + (sfetch ? sunit : 0);
+  const float* sdyp = a.dy + srow0 * a.lddy + (sfetch ? dir * H + sunit : 0);
+  const int cgate = (sid % U) / (U / 4), cunit = u0 + ((sid % U) % (U / 4)) * 4;
+  const bool sstore = SSTORE && sthr && tw == 0 && sbg < B && cunit < H;
+  float* sdp = a.da[dir] + (sstore ? ((size_t)tfirst * B + sbg) * (4 * H) + cgate * H + cunit : 0);
+  const int stoff = sthr ? (sid / U) * LDA + cgate * U + (cunit - u0) : 0;
+
   // wait for the NI partial sums of this thread's chunk published in ring slot `sbase`, phase `par`;
   // their sum goes to psum
   auto exchange = [&](auto ni_c, const unsigned sbase, const unsigned par, const int s) {
@@ -1280,18 +1325,73 @@ __global__ __launch_bounds__(512) void lstm_bwd_rs_kernel(LstmBwdRsArgs a) {
     *reinterpret_cast<f32x4*>(&psum[qq * OWN + within * 4]) = sum;
   };
 
-  for (int s = 0; s < T; ++s) {
-    const int t = dir ? s : (T - 1 - s);
-    const int t_cprev = dir ? (t + 1) : (t - 1);
-
-    TRACE(0);
-    float gv[4] = {0.f, 0.f, 0.f, 0.f}, cv = 0.f, cpv = 0.f, dyv = 0.f;
+  // the owner's words of the current step.  The cell value is carried: the c_{t-1} (in forward time) of
+  // step s is the c_t of step s + 1, so only the first step loads c_t itself; past the sequence's first
+  // time step c_{t-1} = 0
+  float gv[4] = {0.f, 0.f, 0.f, 0.f}, cv = 0.f, cpv = 0.f, dyv = 0.f;
+  if (owner) cv = cp[0];
+  float pend[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // a shadow's words in flight: those of step s + 1
+  if constexpr (SHADOW) {
+    // prologue: the owners fetch step 0 themselves (nothing to wait for yet), the shadows step 1
     if (owner) {
       gv[0] = gp[0]; gv[1] = gp[H]; gv[2] = gp[2 * H]; gv[3] = gp[3 * H];
-      cv = cp[0];
-      if (t_cprev >= 0 && t_cprev < T) cpv = cp[cprev_d];
+      if (T > 1) cpv = cp[cprev_d];
       dyv = dyp[0];
     }
+  }
+  // what the gate derivatives need besides dh, computed at the step's top while the exchange loads fly,
+  // and the operands of the previous step's bias-gradient terms (db_add), added there as well
+  float tc = 0.f, omt = 0.f, omi = 0.f, omf = 0.f, omo = 0.f;
+  float dbl[4] = {0.f, 0.f, 0.f, 0.f};
+  // db += da of the step before: da = dbl x (ig | 1 - ig | 1 - fg | 1 - og) with that product fused into
+  // the sum, one rounding per term
+  auto db_add = [&]() {
+    dbacc[0] = __builtin_fmaf(dbl[0], gv[1], dbacc[0]);
+    dbacc[1] = __builtin_fmaf(dbl[1], omi, dbacc[1]);
+    dbacc[2] = __builtin_fmaf(dbl[2], omf, dbacc[2]);
+    dbacc[3] = __builtin_fmaf(dbl[3], omo, dbacc[3]);
+  };
+  auto pre_math = [&]() {
+#pragma clang fp contract(off)
+    tc = tanh_hw(cv);
+    const float tc2 = tc * tc;
+    omt = 1.f - tc2; omi = 1.f - gv[1]; omf = 1.f - gv[2]; omo = 1.f - gv[3];
+  };
+  // a shadow's global traffic: the words of step f into `pend`, da of step d out of its tile
+  auto shadow_fetch = [&](const int f) {
+    sgp += gstep; scp += cstep; sdyp += ystep;
+    if (sfetch && f < T) {
+      pend[0] = sgp[0]; pend[1] = sgp[H]; pend[2] = sgp[2 * H]; pend[3] = sgp[3 * H];
+      pend[4] = (f + 1 < T) ? scp[cprev_d] : 0.f;
+      pend[5] = sdyp[0];
+    }
+  };
+  auto shadow_store = [&](const int d) {
+    if (sstore) {
+      *reinterpret_cast<f32x4*>(sdp) = *reinterpret_cast<const f32x4*>(&atile[(d & 1) * ATILE + stoff]);
+      sdp += gstep;
+    }
+  };
+
+  if constexpr (SHADOW) shadow_fetch(1);
+  for (int s = 0; s < T; ++s) {
+    TRACE(0);
+    if (othr) {
+      if constexpr (PRE) db_add();
+      if constexpr (SHADOW) {
+        if (s > 0) {
+          const float* ab = &act[(s & 1) * 6 * OWN + tid];
+          gv[0] = ab[0]; gv[1] = ab[OWN]; gv[2] = ab[2 * OWN]; gv[3] = ab[3 * OWN];
+          cpv = ab[4 * OWN]; dyv = ab[5 * OWN];
+        }
+      } else if (owner) {
+        gv[0] = gp[0]; gv[1] = gp[H]; gv[2] = gp[2 * H]; gv[3] = gp[3 * H];
+        cpv = (s + 1 < T) ? cp[cprev_d] : 0.f;
+        dyv = dyp[0];
+      }
+      if constexpr (PRE) { if (owner) pre_math(); }
+    }
+    if constexpr (DRAIN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     if (s > 0) {
       // NI (loads per thread and poll) is a launch constant: one switch per step onto code with
@@ -1316,16 +1416,23 @@ __global__ __launch_bounds__(512) void lstm_bwd_rs_kernel(LstmBwdRsArgs a) {
 #pragma unroll
         for (int k = 0; k < PPR; ++k) dh += psum[k * OWN + tid];
       }
+      if constexpr (!PRE) { if (owner) pre_math(); }
       if (owner) {
+        // dc = dc_state + dh og (1 - tc tc); da = dc ig | dc g ig (1 - ig) | dc c_{t-1} fg (1 - fg) |
+        // dh tc og (1 - og), multiplied left to right.  Every rounding is spelled out (no contraction but
+        // the two written ones: dc here, the bias gradient in db_add), so that moving a term between
+        // the step's top and this phase cannot change a bit of da, dc_state or db
+#pragma clang fp contract(off)
         const float g = gv[0], ig = gv[1], fg = gv[2], og = gv[3];
-        const float tc = tanh_hw(cv);
-        const float dc = dc_state + dh * og * (1.f - tc * tc);
-        dav[0] = dc * ig;
-        dav[1] = dc * g * ig * (1.f - ig);
-        dav[2] = dc * cpv * fg * (1.f - fg);
-        dav[3] = dh * tc * og * (1.f - og);
+        const float dc = __builtin_fmaf(dh * og, omt, dc_state);
+        dbl[0] = dc; dbl[1] = dc * g * ig; dbl[2] = dc * cpv * fg; dbl[3] = dh * tc * og;
+        dav[0] = dbl[0] * ig;
+        dav[1] = dbl[1] * omi;
+        dav[2] = dbl[2] * omf;
+        dav[3] = dbl[3] * omo;
         dc_state = dc * fg;
-        dbacc[0] += dav[0]; dbacc[1] += dav[1]; dbacc[2] += dav[2]; dbacc[3] += dav[3];
+        cv = cpv;
+        if constexpr (!PRE) db_add();
       }
       if constexpr (OWNSPLIT) {
         uint32_t ph[2], pm[2], pl[2];
@@ -1340,9 +1447,20 @@ __global__ __launch_bounds__(512) void lstm_bwd_rs_kernel(LstmBwdRsArgs a) {
           pp[2 * PPST] = (uint16_t)((g & 1) ? (lv >> 16) : (lv & 0xFFFFu));
         }
       } else {
-        float* ap = &atile[orow * LDA + oj];
+        float* ap = &atile[(SSTORE ? (s & 1) * ATILE : 0) + orow * LDA + oj];
         ap[0] = dav[0]; ap[U] = dav[1]; ap[2 * U] = dav[2]; ap[3 * U] = dav[3];
       }
+    } else if (sthr) {
+      // hand step s + 1's words over (fetched a step ago: the exchange wait behind them has drained
+      // the loads), then fetch step s + 2's; the exchange loads of step s + 1 come behind the barrier
+      if (SHADOW && s + 1 < T) {
+        float* ab = &act[((s + 1) & 1) * 6 * OWN + sid];
+        ab[0] = pend[0]; ab[OWN] = pend[1]; ab[2 * OWN] = pend[2]; ab[3 * OWN] = pend[3];
+        ab[4 * OWN] = pend[4]; ab[5 * OWN] = pend[5];
+      }
+      if constexpr (SHADOW) shadow_fetch(s + 2);
+      // da of step s - 1 (twin 0): the other half of the tile, complete since the barrier before last
+      if (s > 0) shadow_store(s - 1);
     }
     __syncthreads();
     TRACE(3);
@@ -1352,7 +1470,8 @@ __global__ __launch_bounds__(512) void lstm_bwd_rs_kernel(LstmBwdRsArgs a) {
       if constexpr (!OWNSPLIT) {
 #pragma unroll
         for (int kg = 0; kg < KG; ++kg)
-          bq[kg] = *reinterpret_cast<const f32x4*>(&atile[fr * LDA + kg * 16 + fq * 4]);
+          bq[kg] = *reinterpret_cast<const f32x4*>(
+              &atile[(SSTORE ? (s & 1) * ATILE : 0) + fr * LDA + kg * 16 + fq * 4]);
       }
       // NACC independent accumulators per tile: a single dependent 16x16x4 chain
       // cannot issue back to back
@@ -1425,27 +1544,36 @@ __global__ __launch_bounds__(512) void lstm_bwd_rs_kernel(LstmBwdRsArgs a) {
     // step s + 1 reads what step s published; the publishing slot walks the ring, its phase flips per lap
     rslot = pslot; rpar = ppar;
     if (++pslot == (unsigned)a.D) { pslot = 0u; ppar ^= 1u; }
-    // da_t is only read by later kernels: plain stores, off the critical path
-    if (owner && tw == 0) {
-      dp[0] = dav[0]; dp[H] = dav[1]; dp[2 * H] = dav[2]; dp[3 * H] = dav[3];
+    // da_t is only read by later kernels: plain stores, off the critical path (the shadows' where
+    // there are any)
+    if constexpr (!SSTORE) {
+      if (owner && tw == 0) {
+        dp[0] = dav[0]; dp[H] = dav[1]; dp[2 * H] = dav[2]; dp[3 * H] = dav[3];
+      }
+      dp += gstep;
     }
-    gp += gstep; dp += gstep; cp += cstep; dyp += ystep;
+    if constexpr (!SHADOW) { gp += gstep; cp += cstep; dyp += ystep; }
     TRACE(5);
   }
+  // the last step's da and bias-gradient terms
+  shadow_store(T - 1);
+  if constexpr (PRE) { if (othr) db_add(); }
   // partial db of the cluster (twin 0): the own 4U da columns summed over the 16 rows, so the
   // caller needs no column-sum kernels (6 launches per step at cfg 2, and a cross-stream join
   // at the tail of backward)
   if (a.dbslab != nullptr && tw == 0) {
+    // (staged in the half of the tile that the last step's da is not in)
+    float* dbt = &atile[SSTORE ? (T & 1) * ATILE : 0];
     __syncthreads();
     if (othr) {
-      float* ap = &atile[orow * LDA + oj];
+      float* ap = &dbt[orow * LDA + oj];
       ap[0] = dbacc[0]; ap[U] = dbacc[1]; ap[2 * U] = dbacc[2]; ap[3 * U] = dbacc[3];
     }
     __syncthreads();
     if (tid < 4 * U) {
       float v = 0.f;
 #pragma unroll
-      for (int rr = 0; rr < 16; ++rr) v += atile[rr * LDA + tid];
+      for (int rr = 0; rr < 16; ++rr) v += dbt[rr * LDA + tid];
       const int gate = tid / U, j = tid % U;
       if (u0 + j < H) a.dbslab[(size_t)cl * (4 * H) + gate * H + u0 + j] = v;
     }
