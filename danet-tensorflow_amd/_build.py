@@ -1,5 +1,5 @@
 '''
-Builds the fourteen HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the fifteen HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -20,6 +20,7 @@ Builds the fourteen HIP libraries (gfx950 only) in-tree with hipcc.
                                                            csrc/{ext_core,adam_one,sumsq_f64}.h
     libdanet_dpcl_hip.so          csrc/dpcl/*.hip          include/danet_dpcl_hip.h, csrc/ext_core.h
     libdanet_neval_hip.so         csrc/neval/*.hip         include/danet_neval_hip.h, csrc/{wave_metric,ext_core}.h
+    libdanet_stitch_hip.so        csrc/stitch/*.hip        include/danet_stitch_hip.h, csrc/ext_core.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -82,6 +83,10 @@ GCLIP = _extension('gclip', *_shared('ext_core', 'adam_one', 'sumsq_f64'))
 DPCL = _extension('dpcl', *_shared('ext_core'))
 NEVAL = _extension('neval', *_shared('wave_metric', 'ext_core'))
 EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL, NEVAL)
+# EXTENSIONS stays the seven records above (tests/test_neval_cpu.py pins it).  Every library after them goes HERE,
+# appended: build_all() runs over MORE_EXTENSIONS after EXTENSIONS
+STITCH = _extension('stitch', *_shared('ext_core'))
+MORE_EXTENSIONS = (STITCH,)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out
 LEVEL_LIB = LEVEL.out
@@ -89,6 +94,7 @@ WAVLOSS_LIB = WAVLOSS.out
 GCLIP_LIB = GCLIP.out
 DPCL_LIB = DPCL.out
 NEVAL_LIB = NEVAL.out
+STITCH_LIB = STITCH.out
 
 
 def _sources(src_dir):
@@ -151,11 +157,11 @@ def build(force=False, verbose=True):
 
 
 def build_all(force=False, verbose=True):
-    '''build(), then every record of EXTENSIONS -> [every shared object built, in order]'''
+    '''build(), then every record of EXTENSIONS and MORE_EXTENSIONS -> [every shared object built, in order]'''
     build(force, verbose)
-    for spec in EXTENSIONS:
+    for spec in EXTENSIONS + MORE_EXTENSIONS:
         _build_spec(spec, force, verbose)
-    return [spec.out for spec in LIBRARIES + LATER_LIBRARIES + EXTENSIONS]
+    return [spec.out for spec in LIBRARIES + LATER_LIBRARIES + EXTENSIONS + MORE_EXTENSIONS]
 
 
 def build_conv(force=False, verbose=True):
@@ -208,6 +214,10 @@ def build_dpcl(force=False, verbose=True):
 
 def build_neval(force=False, verbose=True):
     return _build_spec(NEVAL, force, verbose)
+
+
+def build_stitch(force=False, verbose=True):
+    return _build_spec(STITCH, force, verbose)
 
 
 def build_variant(name, defs):

@@ -1,8 +1,8 @@
 '''
-ctypes binding of the fourteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
-libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip, dpcl and neval
-extension libraries.  Each is described
-once, by a record of ALL_LIBRARIES, LATER_LIBRARIES or EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
+ctypes binding of the fifteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip, dpcl, neval and
+stitch extension libraries.  Each is described
+once, by a record of ALL_LIBRARIES, LATER_LIBRARIES, EXTENSIONS or MORE_EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
 RuntimeError is raised.  PyTorch is used only to own device memory and streams;
@@ -244,15 +244,26 @@ NEVAL_PROTOTYPES = {
     'danet_neval_si_sdr': (c_int, [c_p, c_int, c_int, c_p, c_p, c_p, c_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_stitch_hip.h
+STITCH_PROTOTYPES = {
+    'danet_stitch_abi_version': (c_int, []),
+    'danet_stitch_last_error': (ctypes.c_char_p, []),
+    'danet_stitch_chunks': (c_int, [c_int, c_int, c_int]),
+    'danet_stitch_workspace_bytes': (c_sz, [c_int, c_int, c_int, c_int, c_int]),
+    'danet_stitch_affinity': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_sz]),
+    'danet_stitch_assign': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_sz, c_p, c_p]),
+    'danet_stitch_merge': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Fourteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Fifteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
 # records the per-record tests are written against, by position, ALL_LIBRARIES those and SPEED, and
-# _build.LIBRARIES the same six, LATER_LIBRARIES the seventh; every library after them is APPENDED to EXTENSIONS,
-# here and in _build.py (which builds them in build_all), and is served by the same Library record type, _load
-# and _check.
+# _build.LIBRARIES the same six, LATER_LIBRARIES the seventh, EXTENSIONS the next seven; every library after them is
+# APPENDED to MORE_EXTENSIONS, here and in _build.py (which builds them in build_all), and is served by the same
+# Library record type, _load and _check.
 #   name: '' for the core; so: the file under csrc/; path_var / handle_var: the module globals that hold
 #   its path (read when it is loaded: tests and tools assign to it) and its CDLL (None until then);
 #   prefix: danet_<p>abi_version and danet_<p>last_error follow from it; needs: who needs it, for the
@@ -287,9 +298,8 @@ REVERB = Library('reverb', 'libdanet_reverb_hip.so', 'REVERB_LIB_PATH', '_reverb
 LIBRARIES = (CORE, CONV, DROPOUT, PREP, MIX)
 ALL_LIBRARIES = LIBRARIES + (SPEED,)
 LATER_LIBRARIES = (REVERB,)
-# The three tuples above are closed (tests pin them by length and content).  EXTENSIONS is the OPEN tuple: every
-# library from the eighth on is appended to it, here and in _build.py, and nothing pins its length -- a test of a
-# new library asserts `ITS_RECORD in EXTENSIONS`, never what else is there.
+# The three tuples above are closed (tests pin them by length and content).  EXTENSIONS was the open tuple of the
+# eighth to the fourteenth library (MORE_EXTENSIONS, below it, is today's).
 # loaded at the first valid / test step with EVAL_SI_SDR true only (ops.si_sdr): a run with the key null never
 # maps it
 METRIC_ABI_VERSION = 1
@@ -325,7 +335,17 @@ DPCL = Library('dpcl', 'libdanet_dpcl_hip.so', 'DPCL_LIB_PATH', '_dpcl', DPCL_PR
 NEVAL_ABI_VERSION = 1
 NEVAL = Library('neval', 'libdanet_neval_hip.so', 'NEVAL_LIB_PATH', '_neval', NEVAL_PROTOTYPES,
                 NEVAL_ABI_VERSION, 'danet_neval_', 'NOISE_EVAL_DIR with EVAL_SI_SDR needs the HIP extension library')
+# loaded at the first Model.infer of a recording longer than INFER_CHUNK_LEN frames only (ops.stitch): a run with the
+# key null, and an input of at most one chunk, never maps it
+STITCH_ABI_VERSION = 1
+STITCH = Library('stitch', 'libdanet_stitch_hip.so', 'STITCH_LIB_PATH', '_stitch', STITCH_PROTOTYPES,
+                 STITCH_ABI_VERSION, 'danet_stitch_', 'INFER_CHUNK_LEN needs the HIP extension library')
 EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL, NEVAL)
+# EXTENSIONS is closed too by now: tests/test_neval_cpu.py pins it as the six libraries in front of NEVAL and NEVAL, here
+# and in _build.py.  MORE_EXTENSIONS is the tuple every library from the fifteenth on is appended to, here and in
+# _build.py (build_all runs over it after EXTENSIONS); a test of a new library asserts `ITS_RECORD in MORE_EXTENSIONS`
+# and that its record follows the ones that were there, never the tuple's length or what else it holds.
+MORE_EXTENSIONS = (STITCH,)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -342,8 +362,9 @@ WAVLOSS_LIB_PATH = os.path.join(_CSRC, WAVLOSS.so)
 GCLIP_LIB_PATH = os.path.join(_CSRC, GCLIP.so)
 DPCL_LIB_PATH = os.path.join(_CSRC, DPCL.so)
 NEVAL_LIB_PATH = os.path.join(_CSRC, NEVAL.so)
+STITCH_LIB_PATH = os.path.join(_CSRC, STITCH.so)
 _lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = _gclip = _dpcl = None
-_neval = None
+_neval = _stitch = None
 _lock = threading.Lock()
 
 
@@ -545,6 +566,17 @@ def load_neval():
 def neval_check(rc):
     if rc != 0:
         _check(NEVAL, rc)
+
+
+def load_stitch():
+    if _stitch is not None:
+        return _stitch
+    return _load(STITCH)
+
+
+def stitch_check(rc):
+    if rc != 0:
+        _check(STITCH, rc)
 
 
 # ---- switches ------------------------------------------------------------------

@@ -44,6 +44,11 @@ unchanged.  Differences, all deliberate:
   `GRAD_CLIP_THRES`; the step then also returns `grad_norm` and `clip_coef`.
 * `DPCL_WEIGHT` (a finite number >= 0, default None = off) adds that many times the deep-clustering affinity loss of
   the embedding against the ideal binary mask to what `Model.train_step` minimises; the step then also returns `DPCL`.
+* `INFER_CHUNK_LEN` (frames, a multiple of `LENGTH_ALIGN`, >= 2; default None = off) makes `Model.infer` separate a
+  recording longer than that in overlapping chunks batched through the encoder and stitch them back together with
+  speaker-continuity tracking; `INFER_CHUNK_OVERLAP` (frames of cross-fade, 1 <= V <= L // 2, default None =
+  max(1, L // 4)) and `INFER_CHUNK_BATCH` (chunks per encoder launch group, >= 1, default None = 16) need it;
+  `train_step`, `valid_step` and `debug_fetch` never look at them.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -131,6 +136,12 @@ DEFAULTS = {
     # labels) added to the training loss; None = off, 0.0 = computed and reported but without effect (not in the
     # reference; include/danet_dpcl_hip.h)
     'DPCL_WEIGHT': None,
+    # chunked inference of long recordings: the chunk length in frames (a multiple of LENGTH_ALIGN, >= 2), the
+    # cross-fade length in frames (1 <= V <= L // 2; None = max(1, L // 4)) and the number of chunks per encoder launch
+    # group (>= 1; None = 16); INFER_CHUNK_LEN None = off (not in the reference; include/danet_stitch_hip.h)
+    'INFER_CHUNK_LEN': None,
+    'INFER_CHUNK_OVERLAP': None,
+    'INFER_CHUNK_BATCH': None,
 }
 
 

@@ -75,6 +75,9 @@ class Model(object):
         self._gclip_partials = None
         # None: off; a float: the weight of the deep-clustering auxiliary loss (build() sets it from DPCL_WEIGHT)
         self.dpcl_weight = None
+        # None: off; (L, V, G): chunk length, cross-fade and chunks per launch group of chunked inference (build() sets
+        # it from INFER_CHUNK_LEN / INFER_CHUNK_OVERLAP / INFER_CHUNK_BATCH)
+        self.infer_chunk = None
 
     # ------------------------------------------------------------ variables
     def get_variable(self, name, shape, init):
@@ -123,6 +126,8 @@ class Model(object):
         self._gclip_partials = None
         # None: off; a float >= 0: the weight of the deep-clustering auxiliary loss (include/danet_dpcl_hip.h)
         self.dpcl_weight = self._check_dpcl_weight()
+        # None: off; (L, V, G) of chunked inference (include/danet_stitch_hip.h)
+        self.infer_chunk = self._check_infer_chunk()
         self.encoder = hparams.get_encoder()(self, 'encoder')
         self.estimator = hparams.get_estimator(
             hparams.TRAIN_ESTIMATOR_METHOD)(self, 'train_estimator')
@@ -229,6 +234,35 @@ class Model(object):
         if hparams.MAX_N_SIGNAL > ops.DPCL_MAX_C:
             raise ValueError('DPCL_WEIGHT needs MAX_N_SIGNAL <= %d (got %d)' % (ops.DPCL_MAX_C, hparams.MAX_N_SIGNAL))
         return float(v)
+
+    @staticmethod
+    def _check_infer_chunk():
+        '''INFER_CHUNK_LEN / INFER_CHUNK_OVERLAP / INFER_CHUNK_BATCH (all null: off) -> None or (L, V, G); ValueError
+        naming the key that rules the values out'''
+        def integer(key, least):
+            v = getattr(hparams, key, None)
+            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < least):
+                raise ValueError('%s must be null or an integer >= %d (got %r)' % (key, least, v))
+            return v
+        L = integer('INFER_CHUNK_LEN', 2)
+        V = integer('INFER_CHUNK_OVERLAP', 1)
+        G = integer('INFER_CHUNK_BATCH', 1)
+        if L is None:
+            for key, v in (('INFER_CHUNK_OVERLAP', V), ('INFER_CHUNK_BATCH', G)):
+                if v is not None:
+                    raise ValueError('%s is set (%r) while INFER_CHUNK_LEN is null: it needs INFER_CHUNK_LEN' % (key, v))
+            return None
+        if L % hparams.LENGTH_ALIGN:
+            raise ValueError('INFER_CHUNK_LEN must be a multiple of LENGTH_ALIGN = %d (got %d)'
+                             % (hparams.LENGTH_ALIGN, L))
+        if V is None:
+            V = max(1, L // 4)
+        if V > L // 2:
+            raise ValueError('INFER_CHUNK_OVERLAP must be in 1 .. INFER_CHUNK_LEN // 2 = %d (got %d)' % (L // 2, V))
+        if hparams.MAX_N_SIGNAL > ops.STITCH_MAX_C:
+            raise ValueError('INFER_CHUNK_LEN needs MAX_N_SIGNAL <= %d (got %d): the stitching searches at most 24 '
+                             'permutations per pair of chunks' % (ops.STITCH_MAX_C, hparams.MAX_N_SIGNAL))
+        return L, V, 16 if G is None else G
 
     def _flatten(self):
         n = sum(self.vars[k].numel() for k in self._order)
@@ -600,6 +634,12 @@ class Model(object):
         '''`g_sess.run(infer_fetches, {s_mixed_signals: ...})` (main.py:384-385,
         685-690): complex mixture [B,T,F] -> separated complex [B,C,T,F] using
         the inference estimator and the mixture phase (main.py:333-335).'''
+        if self.infer_chunk is not None:
+            if s_mixed_signals.shape[0] != 1:
+                raise ValueError('INFER_CHUNK_LEN is set: infer takes one recording at a time (got a batch of %d)'
+                                 % s_mixed_signals.shape[0])
+            if s_mixed_signals.shape[1] > self.infer_chunk[0]:
+                return self.infer_long(s_mixed_signals)
         B, E = hparams.BATCH_SIZE, hparams.EMBED_SIZE
         ops.poll_status(self.device)
         with torch.no_grad():
@@ -610,6 +650,46 @@ class Model(object):
             res = ops.reattach_phase(s_sep, fe['phasor'])
         ops.step_done(self.device, collective_consistent=not dist.is_dist())
         return res
+
+    def infer_chunks(self, s_chunks):
+        '''the chunks of one recording, complex64 [n, L, F] -> (mags float32 [n, C, L, F], phasor float32
+        [n, L, F, 2]): the separated magnitudes of every chunk BEFORE phase re-attachment, channels in each chunk's own
+        order, and the mixture phasor.  The chunks go through infer's front-end, encoder, inference estimator and
+        separator in groups of INFER_CHUNK_BATCH; the plugins reshape by hparams.BATCH_SIZE, which is the group's size
+        for the duration of the group.  A group size the recurrent kernels refuse surfaces their error unchanged.'''
+        G = self.infer_chunk[2] if self.infer_chunk is not None else 16
+        n, L, F = s_chunks.shape
+        C, E = hparams.MAX_N_SIGNAL, hparams.EMBED_SIZE
+        mags = torch.empty(n, C, L, F, device=self.device)
+        phasor = torch.empty(n, L, F, 2, device=self.device)
+        ops.poll_status(self.device)
+        batch_size = hparams.BATCH_SIZE
+        try:
+            with torch.no_grad():
+                for g0 in range(0, n, G):
+                    g = min(G, n - g0)
+                    hparams.BATCH_SIZE = g
+                    fe = ops.frontend(s_chunks[g0:g0 + g, None].contiguous())
+                    s_embed = self.encoder(fe['mix_log'])
+                    s_attr = self.valid_estimator(s_embed, s_mix_pwr=fe['mix_pwr'])
+                    mags[g0:g0 + g] = self.separator(fe['mix_pwr'], s_attr, s_embed.reshape(g, -1, E))
+                    phasor[g0:g0 + g] = fe['phasor']
+        finally:
+            hparams.BATCH_SIZE = batch_size
+        ops.step_done(self.device, collective_consistent=not dist.is_dist())
+        return mags, phasor
+
+    def infer_long(self, s_mixed_signals):
+        '''infer for a recording longer than one chunk, complex64 [1, T, F] -> [1, C, T, F]: the plan of
+        include/danet_stitch_hip.h cuts it into overlapping chunks (plain tensor slicing), infer_chunks separates them
+        and ops.stitch aligns their channels, cross-fades the overlaps and re-attaches the mixture phase'''
+        L, V, _G = self.infer_chunk
+        T = s_mixed_signals.shape[1]
+        assert s_mixed_signals.shape[0] == 1 and T > L, s_mixed_signals.shape
+        starts = ops.stitch_plan(T, L, V)
+        s_chunks = torch.stack([s_mixed_signals[0, s:s + L] for s in starts])
+        mags, phasor = self.infer_chunks(s_chunks)
+        return ops.stitch(mags, phasor, T, V)[None]
 
     # ------------------------------------------------------- misc (main.py)
     def set_learn_rate(self, lr):

@@ -1223,6 +1223,140 @@ def dpcl_loss(s_embed_flat, s_src_pwr, main, alpha):
     return DpclLossFn.apply(s_embed_flat, s_src_pwr.reshape(B, -1, N), main, alpha)
 
 
+# ---- stitching of chunked inference (include/danet_stitch_hip.h) ---------------------------------------
+# On the extension library libdanet_stitch_hip.so, mapped at the first call: a run with INFER_CHUNK_LEN null, and an
+# input of at most one chunk, never gets here.  Three launches: overlap affinities -> permutation chain -> merge.
+STITCH_MAX_C = 4                                     # DANET_STITCH_MAX_C
+_stitch_ws = {}          # (device index, stream, n, C, L, F, V) -> (scratch, partials, S, perm)
+_stitch_fades = {}       # (device index, V) -> float32 device vector [V]
+
+
+def stitch_chunks(T, L, V):
+    '''n of the plan of include/danet_stitch_hip.h (1 when T <= L): danet_stitch_chunks, a pure host function'''
+    n = _lib.load_stitch().danet_stitch_chunks(int(T), int(L), int(V))
+    if n < 0:
+        _lib.stitch_check(n)
+    return n
+
+
+def stitch_plan(T, L, V):
+    '''the chunk starts [s_0, ..., s_{n-1}] of the plan: s_i = i * (L - V), the last chunk slid back to end at T'''
+    n = stitch_chunks(T, L, V)
+    if n == 1:
+        return [0]
+    return [i * (L - V) for i in range(n - 1)] + [T - L]
+
+
+def stitch_workspace_bytes(T, L, V, C, F):
+    '''danet_stitch_workspace_bytes: the bytes stitch_affinity writes and stitch_assign reads'''
+    return _lib.bytes_or_raise(_lib.load_stitch().danet_stitch_workspace_bytes(int(T), int(L), int(V), int(C), int(F)),
+                               _lib.stitch_check)
+
+
+def stitch_fade(V, dev):
+    '''w_k = (k + 1) / (V + 1), k < V: computed in float64, rounded once to float32, uploaded once per (device, V)'''
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(V))
+    t = _stitch_fades.get(key)
+    if t is None:
+        w = ((np.arange(V, dtype=np.float64) + 1.0) / (V + 1.0)).astype(np.float32)
+        t = _stitch_fades[key] = torch.from_numpy(w).to(dev)
+    return t
+
+
+def _stitch_shapes(mags, T, V):
+    assert mags.is_cuda and mags.dtype == torch.float32 and mags.dim() == 4 and mags.is_contiguous(), \
+        (mags.device, mags.dtype, mags.shape)
+    n, C, L, F = mags.shape
+    assert n == stitch_chunks(T, L, V), (n, T, L, V)
+    return n, C, L, F
+
+
+def stitch_affinity(mags, T, V, ws=None):
+    '''mags float32 [n, C, L, F] -> the per-pair, per-tile float64 partials of S, a uint8 workspace of
+    stitch_workspace_bytes(T, L, V, C, F) bytes (ws: one to write into), ONE launch (danet_stitch_affinity)'''
+    n, C, L, F = _stitch_shapes(mags, T, V)
+    if ws is None:
+        ws = torch.empty(stitch_workspace_bytes(T, L, V, C, F), dtype=torch.uint8, device=mags.device)
+    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == mags.device
+    with _lib.timed('stitch_affinity'):
+        _lib.stitch_check(_lib.load_stitch().danet_stitch_affinity(_lib.stream(), T, L, V, C, F, ptr(mags), ptr(ws),
+                                                                   ws.numel()))
+    return ws
+
+
+def stitch_assign(ws, T, L, V, C, F, out=None):
+    '''the workspace of stitch_affinity -> (S float64 [n - 1, C, C], perm int32 [n, C]), ONE launch of one workgroup
+    (danet_stitch_assign): perm[i][c] is the channel of chunk i that is output channel c.  out: optional (S, perm)'''
+    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()
+    n = stitch_chunks(T, L, V)
+    if out is None:
+        out = (torch.empty(max(n - 1, 0), C, C, dtype=torch.float64, device=ws.device),
+               torch.empty(n, C, dtype=torch.int32, device=ws.device))
+    S, perm = out
+    assert S.dtype == torch.float64 and S.is_contiguous() and S.numel() == (n - 1) * C * C and S.device == ws.device
+    assert perm.dtype == torch.int32 and perm.is_contiguous() and perm.numel() == n * C and perm.device == ws.device
+    with _lib.timed('stitch_assign'):
+        _lib.stitch_check(_lib.load_stitch().danet_stitch_assign(_lib.stream(), T, L, V, C, F, ptr(ws), ws.numel(),
+                                                                 ptr(S), ptr(perm)))
+    return S, perm
+
+
+def stitch_merge(mags, phasor, perm, T, V, fade=None, out=None):
+    '''mags float32 [n, C, L, F], phasor float32 [n, L, F, 2], perm int32 [n, C] -> complex64 [C, T, F]: the owner
+    chunk's magnitudes (cross-faded with the next chunk's on the last V frames of every chunk but the last) times
+    the mixture phasor, ONE launch (danet_stitch_merge).  fade: float32 device vector [V] (default stitch_fade)'''
+    n, C, L, F = _stitch_shapes(mags, T, V)
+    dev = mags.device
+    assert phasor.dtype == torch.float32 and phasor.is_contiguous() and tuple(phasor.shape) == (n, L, F, 2) \
+        and phasor.device == dev, (phasor.dtype, phasor.shape)
+    assert perm.dtype == torch.int32 and perm.is_contiguous() and tuple(perm.shape) == (n, C) and perm.device == dev
+    fade = stitch_fade(V, dev) if fade is None else fade
+    assert fade.dtype == torch.float32 and fade.is_contiguous() and fade.numel() == V and fade.device == dev
+    if out is None:
+        out = torch.empty(C, T, F, dtype=torch.complex64, device=dev)
+    assert out.dtype == torch.complex64 and out.is_contiguous() and tuple(out.shape) == (C, T, F) and out.device == dev
+    with _lib.timed('stitch_merge'):
+        _lib.stitch_check(_lib.load_stitch().danet_stitch_merge(
+            _lib.stream(), T, L, V, C, F, ptr(mags), ptr(phasor), ptr(fade), ptr(perm), ptr(torch.view_as_real(out))))
+    return out
+
+
+def _stitch_workspace(n, C, L, F, T, V, dev):
+    '''(buffer, partials, S, perm): the views one shape cuts out of the grow-only scratch 'stitch' of this (device,
+    stream), each at a multiple of 256 bytes; cached per shape'''
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
+           torch.cuda.current_stream().cuda_stream, n, C, L, F, V, T)
+    hit = _stitch_ws.get(key)
+    if hit is not None and _lib._ws.get(key[:2] + ('stitch',)) is hit[0]:
+        return hit
+    sizes = (stitch_workspace_bytes(T, L, V, C, F), (n - 1) * C * C * 8, n * C * 4)
+    offs, off = [], 0
+    for size in sizes:
+        offs.append(off)
+        off += (size + 255) & ~255
+    buf = _lib.workspace(off, dev, 'stitch')
+    part = buf[offs[0]:offs[0] + sizes[0]]
+    S = buf[offs[1]:offs[1] + sizes[1]].view(torch.float64).view(n - 1, C, C)
+    perm = buf[offs[2]:offs[2] + sizes[2]].view(torch.int32).view(n, C)
+    if len(_stitch_ws) >= 64:
+        _stitch_ws.clear()
+    hit = _stitch_ws[key] = (buf, part, S, perm)
+    return hit
+
+
+def stitch(mags, phasor, T, V):
+    '''the separated chunks of one recording -> its separated spectra: mags float32 [n, C, L, F] (the separator's
+    output per chunk, channels in each chunk's own order), phasor float32 [n, L, F, 2], the plan (T, L, V) of
+    include/danet_stitch_hip.h -> complex64 [C, T, F], output channel c following one speaker across the chunks.
+    Three launches and nothing else on the device, no host synchronisation; the partials, S and the permutation chain
+    live in a scratch cached per shape, the result is the caller's own.'''
+    n, C, L, F = _stitch_shapes(mags, T, V)
+    _buf, part, S, perm = _stitch_workspace(n, C, L, F, T, V, mags.device)
+    stitch_affinity(mags, T, V, ws=part)
+    stitch_assign(part, T, L, V, C, F, out=(S, perm))
+    return stitch_merge(mags, phasor, perm, T, V)
+
+
 # ---------------------------------------------------------------------------
 # LSTM layer (both directions), raw forward / backward on time-major tensors
 # ---------------------------------------------------------------------------
