@@ -13,7 +13,8 @@
 // danet_istft replaces utils.istft (app/utils.py:53-75): per-frame inverse real
 // FFT (float64 like numpy's accumulators) times the window into `ws`, then a
 // gather pass overlap-adds the <= N/S frames covering each output sample and
-// divides by the overlap-added window^2 -- deterministic, no atomics.
+// divides by the overlap-added window^2 (each square rounded to float32, as the
+// reference's `window ** 2.` is) -- deterministic, no atomics.
 #include "common.h"
 
 template <typename T>
@@ -180,8 +181,9 @@ __global__ void istft_ola_kernel(int T, int N, int S, int used,
       const int m = (int)(i - n * S);
       if (m < 0 || m >= N) continue;
       acc += frames[((int64_t)sig * used + n) * N + m];
-      const double w = (double)window[m];
-      wsum += w * w;                                // utils.py:72
+      const float w = window[m];
+      wsum += (double)(w * w);                      // utils.py:72: `window ** 2.` of the float32 window IS
+                                                    // float32 (a 1e-25 entry squares to 0: not divided by)
     }
     out[(int64_t)sig * len + i] = (wsum != 0.0) ? acc / wsum : acc;   // utils.py:73-74
   }
