@@ -649,7 +649,7 @@ __device__ __forceinline__ void sep_pit_perm(const float* __restrict__ records,
         int pm[MAXC];
         nth_perm(C, pq, pm);
         float v = 0.f;
-        for (int i = 0; i < C; ++i) v += rec_s[i * C + pm[i]] * invN;
+        for (int i = 0; i < C; ++i) v = pit_perm_term(rec_s[i * C + pm[i]], invN, v);
         if (pq == 0 || v < best_v) { best = pq; best_v = v; }
       }
       *perm_s = best;

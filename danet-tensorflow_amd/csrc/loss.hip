@@ -127,6 +127,7 @@ extern "C" int danet_pit_mse_bwd(danet_stream_t stream_, int mode, int B, int C,
                                  const float* dloss_dev, float* dsep_pwr) {
   hipStream_t stream = (hipStream_t)stream_;
   DANET_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && C <= MAXC && N > 0, "pit_mse_bwd: bad shape");
+  DANET_CHECK_ARG(mode == 0 || mode == 1, "pit_mse_bwd: mode");
   DANET_CHECK_ARG(src_c64 && sep_pwr && phasor && perm_idx && dsep_pwr, "pit_mse_bwd: null pointer");
   dim3 grid((unsigned)min((int64_t)64, cdiv64(N, 256)), B);
   DISPATCH_C(C, (pit_bwd_kernel<CP><<<grid, 256, 0, stream>>>(

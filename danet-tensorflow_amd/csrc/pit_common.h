@@ -52,6 +52,14 @@ __device__ __forceinline__ float ordered_chunk_sum(const float* __restrict__ pp,
   return s;
 }
 
+// v + r / N of the permutation search, as ONE explicit fused multiply-add: pit_final_kernel and sep_pit_perm
+// (attractor.hip) must arrive at the same index from the same records, ties and near ties included, and
+// `v += r * invN` left the choice between a fused and an unfused form to the compiler, per inlined copy
+// (the unrolled search of sep_pit_perm<3> was contracted differently from permutation to permutation: of
+// two exactly tied permutations it took the second, and the backward ran under another permutation than
+// the one perm_idx reports).
+__device__ __forceinline__ float pit_perm_term(float r, float invN, float v) { return __builtin_fmaf(r, invN, v); }
+
 __device__ __forceinline__ void nth_perm(int C, int p, int* out) {
   int avail[MAXC] = {0, 1, 2, 3};
   int fact = 1;
@@ -101,8 +109,8 @@ static __global__ __launch_bounds__(PIT_FINAL_THREADS) void pit_final_kernel(
         nth_perm(C, p, perm);
         float v = 0.f, sv = 0.f;
         for (int i = 0; i < C; ++i) {                          // ops.py:422-423
-          v += rec[i * C + perm[i]] * invN;
-          sv += rec[16 + i * C + perm[i]] * invN;
+          v = pit_perm_term(rec[i * C + perm[i]], invN, v);
+          sv = pit_perm_term(rec[16 + i * C + perm[i]], invN, sv);
         }
         if (p == 0 || v < best_v) { best = p; best_v = v; best_s = sv; }   // ops.py:424
       }
