@@ -1,5 +1,5 @@
 '''
-Builds the fifteen HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the sixteen HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -21,6 +21,7 @@ Builds the fifteen HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_dpcl_hip.so          csrc/dpcl/*.hip          include/danet_dpcl_hip.h, csrc/ext_core.h
     libdanet_neval_hip.so         csrc/neval/*.hip         include/danet_neval_hip.h, csrc/{wave_metric,ext_core}.h
     libdanet_stitch_hip.so        csrc/stitch/*.hip        include/danet_stitch_hip.h, csrc/ext_core.h
+    libdanet_bss_hip.so           csrc/bss/*.hip           include/danet_bss_hip.h, csrc/ext_core.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -86,7 +87,8 @@ EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL, NEVAL)
 # EXTENSIONS stays the seven records above (tests/test_neval_cpu.py pins it).  Every library after them goes HERE,
 # appended: build_all() runs over MORE_EXTENSIONS after EXTENSIONS
 STITCH = _extension('stitch', *_shared('ext_core'))
-MORE_EXTENSIONS = (STITCH,)
+BSS = _extension('bss', *_shared('ext_core'))
+MORE_EXTENSIONS = (STITCH, BSS)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out
 LEVEL_LIB = LEVEL.out
@@ -95,6 +97,7 @@ GCLIP_LIB = GCLIP.out
 DPCL_LIB = DPCL.out
 NEVAL_LIB = NEVAL.out
 STITCH_LIB = STITCH.out
+BSS_LIB = BSS.out
 
 
 def _sources(src_dir):
@@ -218,6 +221,10 @@ def build_neval(force=False, verbose=True):
 
 def build_stitch(force=False, verbose=True):
     return _build_spec(STITCH, force, verbose)
+
+
+def build_bss(force=False, verbose=True):
+    return _build_spec(BSS, force, verbose)
 
 
 def build_variant(name, defs):

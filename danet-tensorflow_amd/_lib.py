@@ -1,7 +1,7 @@
 '''
-ctypes binding of the fifteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
-libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip, dpcl, neval and
-stitch extension libraries.  Each is described
+ctypes binding of the sixteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip, dpcl, neval,
+stitch and bss extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES, EXTENSIONS or MORE_EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -255,8 +255,20 @@ STITCH_PROTOTYPES = {
     'danet_stitch_merge': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_bss_hip.h
+BSS_PROTOTYPES = {
+    'danet_bss_abi_version': (c_int, []),
+    'danet_bss_last_error': (ctypes.c_char_p, []),
+    'danet_bss_workspace_bytes': (c_sz, [c_int, c_int, c_int]),
+    'danet_bss_xcorr': (c_int, [c_p, c_int, c_int, c_i64, c_int, c_p, c_p, c_p, c_p]),
+    'danet_bss_systems': (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
+    'danet_bss_chol_solve': (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p]),
+    'danet_bss_finalize': (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int,
+                                   c_p, c_p, c_p, c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Fifteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Sixteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -345,7 +357,12 @@ EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL, NEVAL)
 # and in _build.py.  MORE_EXTENSIONS is the tuple every library from the fifteenth on is appended to, here and in
 # _build.py (build_all runs over it after EXTENSIONS); a test of a new library asserts `ITS_RECORD in MORE_EXTENSIONS`
 # and that its record follows the ones that were there, never the tuple's length or what else it holds.
-MORE_EXTENSIONS = (STITCH,)
+# loaded at the first valid / test step with EVAL_BSS_SDR true only (ops.bss_eval): a run with the key null never
+# maps it
+BSS_ABI_VERSION = 1
+BSS = Library('bss', 'libdanet_bss_hip.so', 'BSS_LIB_PATH', '_bss', BSS_PROTOTYPES,
+              BSS_ABI_VERSION, 'danet_bss_', 'EVAL_BSS_SDR needs the HIP extension library')
+MORE_EXTENSIONS = (STITCH, BSS)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -363,8 +380,9 @@ GCLIP_LIB_PATH = os.path.join(_CSRC, GCLIP.so)
 DPCL_LIB_PATH = os.path.join(_CSRC, DPCL.so)
 NEVAL_LIB_PATH = os.path.join(_CSRC, NEVAL.so)
 STITCH_LIB_PATH = os.path.join(_CSRC, STITCH.so)
+BSS_LIB_PATH = os.path.join(_CSRC, BSS.so)
 _lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = _gclip = _dpcl = None
-_neval = _stitch = None
+_neval = _stitch = _bss = None
 _lock = threading.Lock()
 
 
@@ -577,6 +595,17 @@ def load_stitch():
 def stitch_check(rc):
     if rc != 0:
         _check(STITCH, rc)
+
+
+def load_bss():
+    if _bss is not None:
+        return _bss
+    return _load(BSS)
+
+
+def bss_check(rc):
+    if rc != 0:
+        _check(BSS, rc)
 
 
 # ---- switches ------------------------------------------------------------------

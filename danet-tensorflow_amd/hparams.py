@@ -49,6 +49,10 @@ unchanged.  Differences, all deliberate:
   speaker-continuity tracking; `INFER_CHUNK_OVERLAP` (frames of cross-fade, 1 <= V <= L // 2, default None =
   max(1, L // 4)) and `INFER_CHUNK_BATCH` (chunks per encoder launch group, >= 1, default None = 16) need it;
   `train_step`, `valid_step` and `debug_fetch` never look at them.
+* `EVAL_BSS_SDR` (true / false, default None = off) makes `Model.valid_step` also return the BSS-eval v3
+  (`bss_eval_sources`) figures `SDR`, `SIR`, `SAR` and `SDRi` of the separated waveforms, in dB, for every dataset;
+  `EVAL_BSS_FILTER_LEN` (an integer in 1..512, default None = 512) is the length of the allowed distortion filter and
+  needs it; not with `NOISE_EVAL_DIR`; `train_step`, `infer` and `debug_fetch` never compute them.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -142,6 +146,11 @@ DEFAULTS = {
     'INFER_CHUNK_LEN': None,
     'INFER_CHUNK_OVERLAP': None,
     'INFER_CHUNK_BATCH': None,
+    # `valid` / `test` also report the BSS-eval v3 (bss_eval_sources) SDR, SIR, SAR and the SDR improvement over the
+    # mixture, dB: true = on, null / false = off; and the length of the allowed distortion filter, an integer in
+    # 1..512, None = 512, which needs the first key (not in the reference; include/danet_bss_hip.h)
+    'EVAL_BSS_SDR': None,
+    'EVAL_BSS_FILTER_LEN': None,
 }
 
 

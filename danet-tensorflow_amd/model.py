@@ -119,6 +119,8 @@ class Model(object):
         '''create sub-modules (main.py:210-211, 249-250, 263-270), materialise
         variables with one dry forward, then flatten them for the optimiser.'''
         self.eval_si_sdr = self._check_eval_si_sdr()
+        # None: off; an int: the filter length L of the BSS-eval figures (include/danet_bss_hip.h)
+        self.eval_bss = self._check_eval_bss()
         # 'pit-mse': the reference's PIT-MSE on complex spectra; 'si-sdr': -SI-SDR of the separated waveforms
         self.train_loss = self._check_train_loss()
         # None: off; a float: the largest global L2 norm of the gradient (include/danet_gclip_hip.h)
@@ -161,21 +163,47 @@ class Model(object):
             raise ValueError('EVAL_SI_SDR must be null, true or false (got %r)' % (v,))
         if not v:
             return False
+        Model._check_synth_envelope('EVAL_SI_SDR', ops.METRIC_MAX_C)
+        return True
+
+    @staticmethod
+    def _check_synth_envelope(key, max_c):
+        '''the envelope of danet_metric_synth, whose waveforms the metric `key` is taken on; ValueError naming `key`'''
         N, S = hparams.FFT_SIZE, hparams.FFT_STRIDE
         if N < 64 or N > 1024 or N & (N - 1):
-            raise ValueError('EVAL_SI_SDR needs FFT_SIZE to be a power of two in 64..1024 (got FFT_SIZE = %d): the '
-                             'envelope of danet_metric_synth' % N)
+            raise ValueError('%s needs FFT_SIZE to be a power of two in 64..1024 (got FFT_SIZE = %d): the '
+                             'envelope of danet_metric_synth' % (key, N))
         if 2 * S > N:
-            raise ValueError('EVAL_SI_SDR needs FFT_STRIDE <= FFT_SIZE / 2 (got FFT_STRIDE = %d at FFT_SIZE = %d): '
+            raise ValueError('%s needs FFT_STRIDE <= FFT_SIZE / 2 (got FFT_STRIDE = %d at FFT_SIZE = %d): '
                              'beyond half a window the overlap-added squared window can reach 0 at the window '
-                             'edges' % (S, N))
+                             'edges' % (key, S, N))
         if 8 * S < N:
-            raise ValueError('EVAL_SI_SDR needs FFT_STRIDE >= FFT_SIZE / 8 (got FFT_STRIDE = %d at FFT_SIZE = %d): '
+            raise ValueError('%s needs FFT_STRIDE >= FFT_SIZE / 8 (got FFT_STRIDE = %d at FFT_SIZE = %d): '
                              'the frames that overlap one tile of hops must fit in the 64 KiB of LDS the synthesis '
-                             'kernel uses' % (S, N))
-        if hparams.MAX_N_SIGNAL > ops.METRIC_MAX_C:
-            raise ValueError('EVAL_SI_SDR needs MAX_N_SIGNAL <= %d (got %d)' % (ops.METRIC_MAX_C, hparams.MAX_N_SIGNAL))
-        return True
+                             'kernel uses' % (key, S, N))
+        if hparams.MAX_N_SIGNAL > max_c:
+            raise ValueError('%s needs MAX_N_SIGNAL <= %d (got %d)' % (key, max_c, hparams.MAX_N_SIGNAL))
+
+    @staticmethod
+    def _check_eval_bss():
+        '''EVAL_BSS_SDR / EVAL_BSS_FILTER_LEN (null / false: off) -> None or the filter length L; ValueError naming the
+        key that rules the metric out'''
+        v = getattr(hparams, 'EVAL_BSS_SDR', None)
+        if v is not None and not isinstance(v, bool):
+            raise ValueError('EVAL_BSS_SDR must be null, true or false (got %r)' % (v,))
+        L = getattr(hparams, 'EVAL_BSS_FILTER_LEN', None)
+        if L is not None and (isinstance(L, bool) or not isinstance(L, int) or L < 1 or L > ops.BSS_MAX_L):
+            raise ValueError('EVAL_BSS_FILTER_LEN must be null or an integer in 1..%d (got %r)' % (ops.BSS_MAX_L, L))
+        if not v:
+            if L is not None:
+                raise ValueError('EVAL_BSS_FILTER_LEN is set but EVAL_BSS_SDR is not: the filter length needs the metric')
+            return None
+        if getattr(hparams, 'NOISE_EVAL_DIR', None) is not None:
+            raise ValueError('EVAL_BSS_SDR cannot be combined with NOISE_EVAL_DIR: the BSS-eval baseline of a noisy '
+                             'mixture is not implemented')
+        # the waveforms are those of danet_metric_synth: EVAL_SI_SDR's rules, under this key's name
+        Model._check_synth_envelope('EVAL_BSS_SDR', min(ops.BSS_MAX_C, ops.METRIC_MAX_C))
+        return ops.BSS_MAX_L if L is None else L
 
     @staticmethod
     def _check_train_loss():
@@ -623,10 +651,20 @@ class Model(object):
         with torch.no_grad():
             out = self.forward(s_src_signals, with_valid=True, with_train=False)
             res = dict(loss=out['valid_loss'], SNR=out['valid_SNR'])
+            wav = None
             if self.eval_si_sdr:
                 # the waveform metric does its own permutation search: the estimates go in unpermuted
                 est = ops.reattach_phase(out['sep_pwr_valid'], out['phasor'])
-                res['SI-SDR'], res['SI-SDRi'] = ops.si_sdr(s_src_signals, est)[:2]
+                if self.eval_bss is None:
+                    res['SI-SDR'], res['SI-SDRi'] = ops.si_sdr(s_src_signals, est)[:2]
+                else:
+                    res['SI-SDR'], res['SI-SDRi'], _, _, wav = ops.si_sdr_wav(s_src_signals, est)
+            if self.eval_bss is not None:
+                # BSS-eval on the same waveforms (synthesised once); its permutation is its own too
+                if wav is None:
+                    est = ops.reattach_phase(out['sep_pwr_valid'], out['phasor'])
+                res['SDR'], res['SIR'], res['SAR'], res['SDRi'] = ops.bss_eval(
+                    s_src_signals, est, self.eval_bss, wav=wav)[:4]
         ops.step_done(self.device, collective_consistent=not dist.is_dist())
         return res
 

@@ -918,6 +918,12 @@ def si_sdr(src, est, fft_stride=None):
     tensors of the caller's own (allocated here, written by the finalize kernel; the waveforms and Gram
     matrices live in a scratch cached per shape).  Three launches and nothing else on the device, no host
     synchronisation.'''
+    return si_sdr_wav(src, est, fft_stride)[:4]
+
+
+def si_sdr_wav(src, est, fft_stride=None):
+    '''si_sdr, and as a fifth result the waveforms it synthesised: float32 [B, 2C, (T - 1) * S], a VIEW of the cached
+    scratch that the next call of this shape on this stream overwrites (ops.bss_eval reads it in the same step)'''
     from .hparams import hparams
     S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
     B, C, T, F = src.shape
@@ -929,7 +935,179 @@ def si_sdr(src, est, fft_stride=None):
     mean2, per_utt, perm_idx = metric_finalize(G, out=(torch.empty(B, 2, dtype=torch.float64, device=dev),
                                                        torch.empty(B, dtype=torch.int32, device=dev),
                                                        torch.empty(2, dtype=torch.float64, device=dev)))
-    return mean2[0], mean2[1], per_utt, perm_idx
+    return mean2[0], mean2[1], per_utt, perm_idx, wav
+
+
+# ---- BSS-eval figures of valid / test (include/danet_bss_hip.h) ----------------------------------------
+# On the extension library libdanet_bss_hip.so, mapped at the first call: a run with EVAL_BSS_SDR null never gets
+# here.  waveforms (ops.metric_synth) -> lagged correlations -> block-Toeplitz systems -> two batched Cholesky
+# solves -> decibels, the utterances of a batch in groups whose scratch stays under BSS_SCRATCH_BYTES.
+BSS_MAX_C = 4                                        # DANET_BSS_MAX_C
+BSS_MAX_L = 512                                      # DANET_BSS_MAX_L
+BSS_SCRATCH_BYTES = 256 << 20
+_bss_ws = {}             # (device index, stream, g, C, L) -> (scratch, R, D, ee, G, Gs, Xg, Xs, fg, fs)
+
+
+def bss_workspace_bytes(B, C, L):
+    '''danet_bss_workspace_bytes'''
+    return _lib.bytes_or_raise(_lib.load_bss().danet_bss_workspace_bytes(int(B), int(C), int(L)), _lib.bss_check)
+
+
+def bss_parts(B, C, L):
+    '''[(name, shape, dtype)] of the parts of the buffer of danet_bss_workspace_bytes, in its order'''
+    n, f64, i32 = C * L, torch.float64, torch.int32
+    return [('R', (B, C, C, 2 * L - 1), f64), ('D', (B, C, C, L), f64), ('ee', (B, C), f64), ('G', (B, n, n), f64),
+            ('Gs', (B, C, L, L), f64), ('Xg', (B, C, n), f64), ('Xs', (B, C, C + 1, L), f64), ('fg', (B,), i32),
+            ('fs', (B, C), i32), ('per_utt', (B, 4), f64), ('perm_idx', (B,), i32), ('flags', (B,), i32),
+            ('mean4', (4,), f64)]
+
+
+def _bss_workspace(g, C, L, dev):
+    '''the views a group of g utterances cuts out of the grow-only scratch 'bss' of this (device, stream): a dict by
+    the names of bss_parts; cached per shape'''
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
+           torch.cuda.current_stream().cuda_stream, g, C, L)
+    hit = _bss_ws.get(key)
+    if hit is not None and _lib._ws.get(key[:2] + ('bss',)) is hit[0]:
+        return hit[1]
+    nbytes = bss_workspace_bytes(g, C, L)
+    buf = _lib.workspace(nbytes, dev, 'bss')
+    views, off = {}, 0
+    for name, shape, dtype in bss_parts(g, C, L):
+        n = int(np.prod(shape)) * (8 if dtype == torch.float64 else 4)
+        views[name] = buf[off:off + n].view(dtype).view(shape)
+        off += (n + 255) & ~255
+    assert off == nbytes, (off, nbytes)
+    if len(_bss_ws) >= 64:
+        _bss_ws.clear()
+    _bss_ws[key] = (buf, views)
+    return views
+
+
+def _bss_out(out, shape, dtype, dev):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    assert out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == tuple(shape), \
+        (out.dtype, out.shape, shape)
+    return out
+
+
+def bss_xcorr(wav, filter_len, out=None):
+    '''float32 waveforms [B, 2C, Ls] (references first) -> (R [B, C, C, 2L - 1], D [B, C, C, L], ee [B, C]), float64,
+    ONE launch (danet_bss_xcorr); out: optional (R, D, ee) to write into'''
+    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.is_contiguous() and wav.shape[1] % 2 == 0
+    B, M, Ls = wav.shape
+    C, L, dev = M // 2, int(filter_len), wav.device
+    out = out or (None, None, None)
+    R = _bss_out(out[0], (B, C, C, 2 * L - 1), torch.float64, dev)
+    D = _bss_out(out[1], (B, C, C, L), torch.float64, dev)
+    ee = _bss_out(out[2], (B, C), torch.float64, dev)
+    with _lib.timed('bss_xcorr'):
+        _lib.bss_check(_lib.load_bss().danet_bss_xcorr(_lib.stream(), B, C, Ls, L, ptr(wav), ptr(R), ptr(D), ptr(ee)))
+    return R, D, ee
+
+
+def bss_systems(R, D, out=None):
+    '''R [B, C, C, 2L - 1], D [B, C, C, L] -> (G [B, CL, CL], Gs [B, C, L, L], Xg [B, C, CL], Xs [B, C, C + 1, L]),
+    ONE launch (danet_bss_systems); out: optional tuple of the four to write into'''
+    assert R.is_cuda and R.dtype == torch.float64 and R.dim() == 4 and R.is_contiguous()
+    B, C, L, dev = R.shape[0], R.shape[1], D.shape[3], R.device
+    assert tuple(R.shape) == (B, C, C, 2 * L - 1) and D.dtype == torch.float64 and D.is_contiguous() \
+        and tuple(D.shape) == (B, C, C, L) and D.device == dev, (R.shape, D.shape)
+    out = out or (None,) * 4
+    G = _bss_out(out[0], (B, C * L, C * L), torch.float64, dev)
+    Gs = _bss_out(out[1], (B, C, L, L), torch.float64, dev)
+    Xg = _bss_out(out[2], (B, C, C * L), torch.float64, dev)
+    Xs = _bss_out(out[3], (B, C, C + 1, L), torch.float64, dev)
+    with _lib.timed('bss_systems'):
+        _lib.bss_check(_lib.load_bss().danet_bss_systems(_lib.stream(), B, C, L, ptr(R), ptr(D), ptr(G), ptr(Gs),
+                                                         ptr(Xg), ptr(Xs)))
+    return G, Gs, Xg, Xs
+
+
+def bss_chol_solve(A, X, flags=None):
+    '''IN PLACE: A float64 [nmat, n, n] symmetric positive definite -> its Cholesky factor, X float64 [nmat, nrhs, n]
+    (one right-hand side per row) -> the solutions; -> flags int32 [nmat], 1 where a pivot failed
+    (danet_bss_chol_solve: blocked, the trailing updates of the whole batch on f64 MFMA)'''
+    assert A.is_cuda and A.dtype == torch.float64 and A.dim() == 3 and A.is_contiguous() and A.shape[1] == A.shape[2]
+    nmat, n = A.shape[0], A.shape[1]
+    assert X.dtype == torch.float64 and X.dim() == 3 and X.is_contiguous() and X.device == A.device \
+        and X.shape[0] == nmat and X.shape[2] == n, (A.shape, X.shape)
+    flags = _bss_out(flags, (nmat,), torch.int32, A.device)
+    with _lib.timed('bss_chol_solve'):
+        _lib.bss_check(_lib.load_bss().danet_bss_chol_solve(_lib.stream(), nmat, n, X.shape[1], ptr(A), ptr(X),
+                                                            ptr(flags)))
+    return flags
+
+
+def bss_finalize(R, D, ee, Xg, Xs, fg, fs, b0=0, out=None):
+    '''the correlations, right-hand sides, solutions and factorisation flags of B utterances -> (mean4 [4],
+    per_utt [B_all, 4], perm_idx int32 [B_all], flags int32 [B_all]), ONE launch (danet_bss_finalize): rows b0 ..
+    b0 + B - 1 are written, and mean4 from all rows when b0 + B = B_all.  out: optional (per_utt, perm_idx, flags,
+    mean4) of a batch of B_all utterances to write into (default B_all = B)'''
+    B, C, L, dev = R.shape[0], R.shape[1], D.shape[3], R.device
+    for t, shape, dtype in ((R, (B, C, C, 2 * L - 1), torch.float64), (D, (B, C, C, L), torch.float64),
+                            (ee, (B, C), torch.float64), (Xg, (B, C, C * L), torch.float64),
+                            (Xs, (B, C, C + 1, L), torch.float64), (fg, (B,), torch.int32), (fs, (B, C), torch.int32)):
+        assert t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, \
+            (t.dtype, t.shape, shape)
+    if out is None:
+        out = (torch.empty(B, 4, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.float64, device=dev))
+    per_utt, perm_idx, flags, mean4 = out
+    B_all = per_utt.shape[0]
+    assert per_utt.dtype == torch.float64 and per_utt.is_contiguous() and tuple(per_utt.shape) == (B_all, 4)
+    assert perm_idx.dtype == torch.int32 and perm_idx.is_contiguous() and tuple(perm_idx.shape) == (B_all,)
+    assert flags.dtype == torch.int32 and flags.is_contiguous() and tuple(flags.shape) == (B_all,)
+    assert mean4.dtype == torch.float64 and mean4.is_contiguous() and mean4.numel() == 4
+    with _lib.timed('bss_finalize'):
+        _lib.bss_check(_lib.load_bss().danet_bss_finalize(
+            _lib.stream(), B, C, L, ptr(R), ptr(D), ptr(ee), ptr(Xg), ptr(Xs), ptr(fg), ptr(fs), int(b0), B_all,
+            ptr(per_utt), ptr(perm_idx), ptr(flags), ptr(mean4)))
+    return mean4, per_utt, perm_idx, flags
+
+
+def bss_group(B, C, L):
+    '''the utterances ops.bss_eval takes at a time: the most whose scratch stays under BSS_SCRATCH_BYTES (one at least)'''
+    g = max(1, min(int(B), BSS_SCRATCH_BYTES // bss_workspace_bytes(1, C, L)))
+    while g > 1 and bss_workspace_bytes(g, C, L) > BSS_SCRATCH_BYTES:
+        g -= 1
+    return g
+
+
+def bss_eval(src, est, filter_len=None, fft_stride=None, wav=None, group=None):
+    '''BSS-eval SDR, SIR, SAR and SDRi (dB; the rule of include/danet_bss_hip.h) of the waveforms of the UNPERMUTED
+    estimates `est` against the references `src`, both complex64 [B, C, T, F] -> (sdr, sir, sar, sdri,
+    per_utt [B, 4], perm_idx [B], flags [B]): float64 / int32 device tensors of the caller's own.  wav: the float32
+    waveforms [B, 2C, (T - 1) * S] when they exist already (ops.si_sdr_wav), else they are synthesised here
+    (ops.metric_synth, into the metric's cached scratch).  filter_len: L (default hparams.EVAL_BSS_FILTER_LEN, 512
+    when that is null).  The utterances go through the stages in groups of `group` (default ops.bss_group: the scratch
+    stays under BSS_SCRATCH_BYTES); the batch means are formed on the device over all groups by the last group's
+    finalize launch, so they do not depend on the grouping.  No host synchronisation.'''
+    from .hparams import hparams
+    if filter_len is None:
+        filter_len = getattr(hparams, 'EVAL_BSS_FILTER_LEN', None) or BSS_MAX_L
+    L = int(filter_len)
+    B, C, T, F = src.shape
+    dev = src.device
+    if wav is None:
+        S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
+        wav = _wave_workspace('metric', _metric_ws, 2 * C, 2, B, C, T, 2 * (F - 1), S, dev)[1]
+        metric_synth(src, est, S, out=wav)
+    assert wav.is_cuda and wav.dtype == torch.float32 and wav.is_contiguous() and tuple(wav.shape[:2]) == (B, 2 * C)
+    g = bss_group(B, C, L) if group is None else max(1, min(int(group), B))
+    out = (torch.empty(B, 4, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+           torch.empty(B, dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.float64, device=dev))
+    for b0 in range(0, B, g):
+        nb = min(g, B - b0)
+        w = _bss_workspace(nb, C, L, dev)
+        bss_xcorr(wav[b0:b0 + nb], L, out=(w['R'], w['D'], w['ee']))
+        bss_systems(w['R'], w['D'], out=(w['G'], w['Gs'], w['Xg'], w['Xs']))
+        bss_chol_solve(w['G'], w['Xg'], w['fg'])
+        bss_chol_solve(w['Gs'].view(nb * C, L, L), w['Xs'].view(nb * C, C + 1, L), w['fs'].view(nb * C))
+        bss_finalize(w['R'], w['D'], w['ee'], w['Xg'], w['Xs'], w['fg'], w['fs'], b0=b0, out=out)
+    per_utt, perm_idx, flags, mean4 = out
+    return mean4[0], mean4[1], mean4[2], mean4[3], per_utt, perm_idx, flags
 
 
 # ---- waveform metric of a noisy valid / test sweep (include/danet_neval_hip.h) -------------------------
