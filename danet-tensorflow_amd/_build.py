@@ -1,5 +1,5 @@
 '''
-Builds the sixteen HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the seventeen HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -22,6 +22,7 @@ Builds the sixteen HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_neval_hip.so         csrc/neval/*.hip         include/danet_neval_hip.h, csrc/{wave_metric,ext_core}.h
     libdanet_stitch_hip.so        csrc/stitch/*.hip        include/danet_stitch_hip.h, csrc/ext_core.h
     libdanet_bss_hip.so           csrc/bss/*.hip           include/danet_bss_hip.h, csrc/ext_core.h
+    libdanet_stoi_hip.so          csrc/stoi/*.hip          include/danet_stoi_hip.h, csrc/ext_core.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -88,7 +89,8 @@ EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL, NEVAL)
 # appended: build_all() runs over MORE_EXTENSIONS after EXTENSIONS
 STITCH = _extension('stitch', *_shared('ext_core'))
 BSS = _extension('bss', *_shared('ext_core'))
-MORE_EXTENSIONS = (STITCH, BSS)
+STOI = _extension('stoi', *_shared('ext_core'))
+MORE_EXTENSIONS = (STITCH, BSS, STOI)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out
 LEVEL_LIB = LEVEL.out
@@ -98,6 +100,7 @@ DPCL_LIB = DPCL.out
 NEVAL_LIB = NEVAL.out
 STITCH_LIB = STITCH.out
 BSS_LIB = BSS.out
+STOI_LIB = STOI.out
 
 
 def _sources(src_dir):
@@ -225,6 +228,10 @@ def build_stitch(force=False, verbose=True):
 
 def build_bss(force=False, verbose=True):
     return _build_spec(BSS, force, verbose)
+
+
+def build_stoi(force=False, verbose=True):
+    return _build_spec(STOI, force, verbose)
 
 
 def build_variant(name, defs):

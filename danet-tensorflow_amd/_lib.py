@@ -1,7 +1,7 @@
 '''
-ctypes binding of the sixteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+ctypes binding of the seventeen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
 libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip, dpcl, neval,
-stitch and bss extension libraries.  Each is described
+stitch, bss and stoi extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES, EXTENSIONS or MORE_EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -267,8 +267,20 @@ BSS_PROTOTYPES = {
                                    c_p, c_p, c_p, c_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_stoi_hip.h
+STOI_PROTOTYPES = {
+    'danet_stoi_abi_version': (c_int, []),
+    'danet_stoi_last_error': (ctypes.c_char_p, []),
+    'danet_stoi_workspace_bytes': (c_sz, [c_int, c_int, c_i64, c_int, c_int]),
+    'danet_stoi_resample': (c_int, [c_p, c_int, c_int, c_i64, c_int, c_int, c_p, c_p, c_p]),
+    'danet_stoi_frames': (c_int, [c_p, c_int, c_int, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    'danet_stoi_bands': (c_int, [c_p, c_int, c_int, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    'danet_stoi_segments': (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p]),
+    'danet_stoi_finalize': (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Sixteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Seventeen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -362,7 +374,11 @@ EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL, NEVAL)
 BSS_ABI_VERSION = 1
 BSS = Library('bss', 'libdanet_bss_hip.so', 'BSS_LIB_PATH', '_bss', BSS_PROTOTYPES,
               BSS_ABI_VERSION, 'danet_bss_', 'EVAL_BSS_SDR needs the HIP extension library')
-MORE_EXTENSIONS = (STITCH, BSS)
+# loaded at the first valid / test step with EVAL_STOI true only (ops.stoi_eval): a run with the key null never maps it
+STOI_ABI_VERSION = 1
+STOI = Library('stoi', 'libdanet_stoi_hip.so', 'STOI_LIB_PATH', '_stoi', STOI_PROTOTYPES,
+               STOI_ABI_VERSION, 'danet_stoi_', 'EVAL_STOI needs the HIP extension library')
+MORE_EXTENSIONS = (STITCH, BSS, STOI)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -381,8 +397,9 @@ DPCL_LIB_PATH = os.path.join(_CSRC, DPCL.so)
 NEVAL_LIB_PATH = os.path.join(_CSRC, NEVAL.so)
 STITCH_LIB_PATH = os.path.join(_CSRC, STITCH.so)
 BSS_LIB_PATH = os.path.join(_CSRC, BSS.so)
+STOI_LIB_PATH = os.path.join(_CSRC, STOI.so)
 _lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = _gclip = _dpcl = None
-_neval = _stitch = _bss = None
+_neval = _stitch = _bss = _stoi = None
 _lock = threading.Lock()
 
 
@@ -606,6 +623,17 @@ def load_bss():
 def bss_check(rc):
     if rc != 0:
         _check(BSS, rc)
+
+
+def load_stoi():
+    if _stoi is not None:
+        return _stoi
+    return _load(STOI)
+
+
+def stoi_check(rc):
+    if rc != 0:
+        _check(STOI, rc)
 
 
 # ---- switches ------------------------------------------------------------------

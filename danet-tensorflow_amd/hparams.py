@@ -53,6 +53,10 @@ unchanged.  Differences, all deliberate:
   (`bss_eval_sources`) figures `SDR`, `SIR`, `SAR` and `SDRi` of the separated waveforms, in dB, for every dataset;
   `EVAL_BSS_FILTER_LEN` (an integer in 1..512, default None = 512) is the length of the allowed distortion filter and
   needs it; not with `NOISE_EVAL_DIR`; `train_step`, `infer` and `debug_fetch` never compute them.
+* `EVAL_STOI` (true / false, default None = off) makes `Model.valid_step` also return the intelligibility figures
+  `STOI`, `ESTOI` and their improvements over the mixture `STOIi`, `ESTOIi` of the separated waveforms, for every
+  dataset; it needs `SMPRATE` >= 8000 with a resampling table to 10 kHz of at most 16384 entries; not with
+  `NOISE_EVAL_DIR`; `train_step`, `infer` and `debug_fetch` never compute them.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -151,6 +155,9 @@ DEFAULTS = {
     # 1..512, None = 512, which needs the first key (not in the reference; include/danet_bss_hip.h)
     'EVAL_BSS_SDR': None,
     'EVAL_BSS_FILTER_LEN': None,
+    # `valid` / `test` also report STOI, ESTOI and the improvement of each over the mixture, on the waveforms
+    # resampled to 10 kHz: true = on, null / false = off (not in the reference; include/danet_stoi_hip.h)
+    'EVAL_STOI': None,
 }
 
 

@@ -121,6 +121,8 @@ class Model(object):
         self.eval_si_sdr = self._check_eval_si_sdr()
         # None: off; an int: the filter length L of the BSS-eval figures (include/danet_bss_hip.h)
         self.eval_bss = self._check_eval_bss()
+        # STOI / ESTOI of the separated waveforms (include/danet_stoi_hip.h)
+        self.eval_stoi = self._check_eval_stoi()
         # 'pit-mse': the reference's PIT-MSE on complex spectra; 'si-sdr': -SI-SDR of the separated waveforms
         self.train_loss = self._check_train_loss()
         # None: off; a float: the largest global L2 norm of the gradient (include/danet_gclip_hip.h)
@@ -204,6 +206,24 @@ class Model(object):
         # the waveforms are those of danet_metric_synth: EVAL_SI_SDR's rules, under this key's name
         Model._check_synth_envelope('EVAL_BSS_SDR', min(ops.BSS_MAX_C, ops.METRIC_MAX_C))
         return ops.BSS_MAX_L if L is None else L
+
+    @staticmethod
+    def _check_eval_stoi():
+        '''EVAL_STOI (null / false: off) -> bool; ValueError naming the key that rules the metric out'''
+        v = getattr(hparams, 'EVAL_STOI', None)
+        if v is not None and not isinstance(v, bool):
+            raise ValueError('EVAL_STOI must be null, true or false (got %r)' % (v,))
+        if not v:
+            return False
+        if getattr(hparams, 'NOISE_EVAL_DIR', None) is not None:
+            raise ValueError('EVAL_STOI cannot be combined with NOISE_EVAL_DIR: the intelligibility baseline of a '
+                             'noisy mixture is not implemented')
+        # the waveforms are those of danet_metric_synth: EVAL_SI_SDR's rules, under this key's name
+        Model._check_synth_envelope('EVAL_STOI', min(ops.STOI_MAX_C, ops.METRIC_MAX_C))
+        ops.stoi_rate(hparams.SMPRATE)                       # ValueError naming EVAL_STOI and SMPRATE
+        return True
+
+    _stoi_key = _check_eval_stoi
 
     @staticmethod
     def _check_train_loss():
@@ -655,16 +675,21 @@ class Model(object):
             if self.eval_si_sdr:
                 # the waveform metric does its own permutation search: the estimates go in unpermuted
                 est = ops.reattach_phase(out['sep_pwr_valid'], out['phasor'])
-                if self.eval_bss is None:
+                if self.eval_bss is None and not self.eval_stoi:
                     res['SI-SDR'], res['SI-SDRi'] = ops.si_sdr(s_src_signals, est)[:2]
                 else:
                     res['SI-SDR'], res['SI-SDRi'], _, _, wav = ops.si_sdr_wav(s_src_signals, est)
+            elif self.eval_bss is not None or self.eval_stoi:
+                est = ops.reattach_phase(out['sep_pwr_valid'], out['phasor'])
+                if self.eval_bss is not None and self.eval_stoi:
+                    # both read the waveforms: synthesised once, into the metric's cached scratch
+                    wav = ops.synth_wav(s_src_signals, est)
             if self.eval_bss is not None:
                 # BSS-eval on the same waveforms (synthesised once); its permutation is its own too
-                if wav is None:
-                    est = ops.reattach_phase(out['sep_pwr_valid'], out['phasor'])
                 res['SDR'], res['SIR'], res['SAR'], res['SDRi'] = ops.bss_eval(
                     s_src_signals, est, self.eval_bss, wav=wav)[:4]
+            if self.eval_stoi:
+                res['STOI'], res['ESTOI'], res['STOIi'], res['ESTOIi'] = ops.stoi_eval(s_src_signals, est, wav=wav)[:4]
         ops.step_done(self.device, collective_consistent=not dist.is_dist())
         return res
 

@@ -938,6 +938,17 @@ def si_sdr_wav(src, est, fft_stride=None):
     return mean2[0], mean2[1], per_utt, perm_idx, wav
 
 
+def synth_wav(src, est, fft_stride=None):
+    '''the float32 waveforms [B, 2C, (T - 1) * S] of the references and the UNPERMUTED estimates, synthesised into the
+    metric's cached scratch (a VIEW the next call of this shape on this stream overwrites): what ops.bss_eval and
+    ops.stoi_eval synthesise for themselves when no `wav` is given, once for both'''
+    from .hparams import hparams
+    S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
+    B, C, T, F = src.shape
+    wav = _wave_workspace('metric', _metric_ws, 2 * C, 2, B, C, T, 2 * (F - 1), S, src.device)[1]
+    return metric_synth(src, est, S, out=wav)
+
+
 # ---- BSS-eval figures of valid / test (include/danet_bss_hip.h) ----------------------------------------
 # On the extension library libdanet_bss_hip.so, mapped at the first call: a run with EVAL_BSS_SDR null never gets
 # here.  waveforms (ops.metric_synth) -> lagged correlations -> block-Toeplitz systems -> two batched Cholesky
@@ -1108,6 +1119,246 @@ def bss_eval(src, est, filter_len=None, fft_stride=None, wav=None, group=None):
         bss_finalize(w['R'], w['D'], w['ee'], w['Xg'], w['Xs'], w['fg'], w['fs'], b0=b0, out=out)
     per_utt, perm_idx, flags, mean4 = out
     return mean4[0], mean4[1], mean4[2], mean4[3], per_utt, perm_idx, flags
+
+
+# ---- STOI / ESTOI of valid / test (include/danet_stoi_hip.h) -------------------------------------------
+# On the extension library libdanet_stoi_hip.so, mapped at the first call: a run with EVAL_STOI null never gets
+# here.  waveforms (ops.metric_synth) -> 10 kHz rows with the mixture -> silent frames of every reference -> band
+# magnitudes of the compacted frames -> segment correlations -> permutation search and batch means.
+STOI_MAX_C = 4                                       # DANET_STOI_MAX_C
+STOI_MAX_TABLE = 16384                               # DANET_STOI_MAX_TABLE
+STOI_FS = 10000
+STOI_MIN_RATE = 8000
+STOI_SCRATCH_BYTES = 256 << 20
+_stoi_ws = {}            # (device index, stream, g, C, Ls, U, D) -> (scratch, views)
+_stoi_tables = {}        # (device index, SMPRATE) -> dict(U, D, H, h, w, tw, bins, bands)
+
+
+def stoi_rate(smprate):
+    '''SMPRATE -> (U, D, H) of the resampling to 10 kHz (H = 0: the stage is a copy); ValueError naming EVAL_STOI and
+    SMPRATE where the table of 2H + 1 entries would not fit or the rate is below 8 kHz'''
+    if isinstance(smprate, bool) or not isinstance(smprate, (int, np.integer)) or smprate < STOI_MIN_RATE:
+        raise ValueError('EVAL_STOI needs SMPRATE to be an integer >= %d: the fifteen bands reach 4.3 kHz (got '
+                         'SMPRATE = %r)' % (STOI_MIN_RATE, smprate))
+    g = math.gcd(STOI_FS, int(smprate))
+    U, D = STOI_FS // g, int(smprate) // g
+    H = 0 if U == D == 1 else 10 * max(U, D)
+    if 2 * H + 1 > STOI_MAX_TABLE:
+        raise ValueError('EVAL_STOI needs an SMPRATE whose resampling table to 10 kHz has at most %d entries (SMPRATE '
+                         '= %d gives U / D = %d / %d and %d entries)' % (STOI_MAX_TABLE, smprate, U, D, 2 * H + 1))
+    return U, D, H
+
+
+def stoi_tables(smprate, dev):
+    '''the inputs the library computes nothing of, uploaded once per (device, SMPRATE): h (float32 [2H + 1]), the
+    window w (float32 [256]), the twiddle factors tw (float64 [256, 2]) and the band bins (a HOST int32 [15][2])'''
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(smprate))
+    t = _stoi_tables.get(key)
+    if t is not None:
+        return t
+    U, D, H = stoi_rate(smprate)
+    if H:
+        import scipy.signal
+        h = U * scipy.signal.firwin(2 * H + 1, 1.0 / max(U, D), window=('kaiser', 5.0))
+    else:
+        h = np.ones(1)
+    grid = np.arange(257) * (STOI_FS / 512.0)
+    edge = lambda e: int(np.argmin(np.abs(grid - 150.0 * 2.0 ** (e / 6.0))))
+    bins = tuple((edge(2 * b - 1), edge(2 * b + 1)) for b in range(15))
+    ang = -2.0 * np.pi * np.arange(256) / 512.0
+    t = dict(U=U, D=D, H=H, bins=bins, bands=(ctypes.c_int32 * 30)(*[v for lo_hi in bins for v in lo_hi]),
+             h=torch.from_numpy(h.astype(np.float32)).to(dev),
+             w=torch.from_numpy(np.hanning(258)[1:-1].astype(np.float32)).to(dev),
+             tw=torch.from_numpy(np.stack([np.cos(ang), np.sin(ang)], axis=1)).to(dev))
+    _stoi_tables[key] = t
+    return t
+
+
+def _stoi_smprate(smprate):
+    from .hparams import hparams
+    return int(hparams.SMPRATE if smprate is None else smprate)
+
+
+def stoi_lengths(Ls, U, D):
+    '''(L10, nf): samples of a 10 kHz row and its frames of 256 at hop 128'''
+    L10 = -(-int(Ls) * U // D)
+    return L10, ((L10 - 256) // 128 + 1 if L10 >= 256 else 0)
+
+
+def stoi_workspace_bytes(B, C, Ls, U, D):
+    '''danet_stoi_workspace_bytes'''
+    return _lib.bytes_or_raise(_lib.load_stoi().danet_stoi_workspace_bytes(int(B), int(C), int(Ls), int(U), int(D)),
+                               _lib.stoi_check)
+
+
+def stoi_parts(B, C, Ls, U, D):
+    '''[(name, shape, dtype)] of the parts of the buffer of danet_stoi_workspace_bytes, in its order'''
+    L10, nf = stoi_lengths(Ls, U, D)
+    n, f32, f64, i32 = max(nf, 1), torch.float32, torch.float64, torch.int32
+    return [('sig', (B, 2 * C + 1, L10), f32), ('E', (B, C, n), f64), ('mask', (B, C, n), i32),
+            ('kidx', (B, C, n), i32), ('M', (B, C), i32), ('Emax', (B, C), f64), ('T', (B, C, C + 2, 15, n), f64),
+            ('d', (B, C, C + 1, 2), f64), ('per_utt', (B, 4), f64), ('perm_idx', (B,), i32), ('flags', (B,), i32),
+            ('mean4', (4,), f64), ('count', (1,), i32)]
+
+
+def _stoi_workspace(g, C, Ls, U, D, dev):
+    '''the views a group of g utterances cuts out of the grow-only scratch 'stoi' of this (device, stream): a dict by
+    the names of stoi_parts; cached per shape'''
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
+           torch.cuda.current_stream().cuda_stream, g, C, Ls, U, D)
+    hit = _stoi_ws.get(key)
+    if hit is not None and _lib._ws.get(key[:2] + ('stoi',)) is hit[0]:
+        return hit[1]
+    nbytes = stoi_workspace_bytes(g, C, Ls, U, D)
+    buf = _lib.workspace(nbytes, dev, 'stoi')
+    views, off = {}, 0
+    for name, shape, dtype in stoi_parts(g, C, Ls, U, D):
+        n = int(np.prod(shape)) * (8 if dtype == torch.float64 else 4)
+        views[name] = buf[off:off + n].view(dtype).view(shape)
+        off += (n + 255) & ~255
+    assert off == nbytes, (off, nbytes)
+    if len(_stoi_ws) >= 64:
+        _stoi_ws.clear()
+    _stoi_ws[key] = (buf, views)
+    return views
+
+
+def stoi_resample(wav, smprate=None, out=None):
+    '''float32 waveforms [B, 2C, Ls] (references first) -> the 10 kHz rows float32 [B, 2C + 1, L10], the last one the
+    mixture of the references, ONE launch (danet_stoi_resample); out: optional tensor to write into'''
+    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.shape[1] % 2 == 0 \
+        and wav.stride(2) == 1 and wav.stride(1) == wav.shape[2] and wav.stride(0) == wav.shape[1] * wav.shape[2], \
+        (wav.dtype, wav.shape, wav.stride())
+    B, R, Ls = wav.shape
+    t = stoi_tables(_stoi_smprate(smprate), wav.device)
+    sig = _bss_out(out, (B, R + 1, stoi_lengths(Ls, t['U'], t['D'])[0]), torch.float32, wav.device)
+    with _lib.timed('stoi_resample'):
+        _lib.stoi_check(_lib.load_stoi().danet_stoi_resample(_lib.stream(), B, R // 2, Ls, t['U'], t['D'], ptr(wav),
+                                                             ptr(t['h']), ptr(sig)))
+    return sig
+
+
+def stoi_frames(sig, smprate=None, out=None):
+    '''the 10 kHz rows [B, 2C + 1, L10] -> (E [B, C, n], mask [B, C, n], kidx [B, C, n], M [B, C], Emax [B, C]) of
+    the C references, n = max(nf, 1), ONE launch (danet_stoi_frames); out: optional tuple of the five'''
+    assert sig.is_cuda and sig.dtype == torch.float32 and sig.dim() == 3 and sig.is_contiguous() and sig.shape[1] % 2
+    B, R, L10 = sig.shape
+    C, dev = R // 2, sig.device
+    n = max((L10 - 256) // 128 + 1 if L10 >= 256 else 0, 1)
+    out = out or (None,) * 5
+    E = _bss_out(out[0], (B, C, n), torch.float64, dev)
+    mask = _bss_out(out[1], (B, C, n), torch.int32, dev)
+    kidx = _bss_out(out[2], (B, C, n), torch.int32, dev)
+    M = _bss_out(out[3], (B, C), torch.int32, dev)
+    Emax = _bss_out(out[4], (B, C), torch.float64, dev)
+    t = stoi_tables(_stoi_smprate(smprate), dev)
+    with _lib.timed('stoi_frames'):
+        _lib.stoi_check(_lib.load_stoi().danet_stoi_frames(_lib.stream(), B, C, L10, ptr(sig), ptr(t['w']), ptr(E),
+                                                           ptr(mask), ptr(kidx), ptr(M), ptr(Emax)))
+    return E, mask, kidx, M, Emax
+
+
+def stoi_bands(sig, kidx, M, smprate=None, out=None):
+    '''the 10 kHz rows, k(.) and M of the references -> the band magnitudes T float64 [B, C, C + 2, 15, n] of the
+    compacted frames of every (reference, paired signal), ONE launch (danet_stoi_bands; none when L10 < 256)'''
+    assert sig.is_cuda and sig.dtype == torch.float32 and sig.dim() == 3 and sig.is_contiguous() and sig.shape[1] % 2
+    B, R, L10 = sig.shape
+    C, dev = R // 2, sig.device
+    n = max((L10 - 256) // 128 + 1 if L10 >= 256 else 0, 1)
+    for t_, shape in ((kidx, (B, C, n)), (M, (B, C))):
+        assert t_.is_cuda and t_.device == dev and t_.dtype == torch.int32 and t_.is_contiguous() \
+            and tuple(t_.shape) == shape, (t_.dtype, t_.shape, shape)
+    T = _bss_out(out, (B, C, C + 2, 15, n), torch.float64, dev)
+    t = stoi_tables(_stoi_smprate(smprate), dev)
+    with _lib.timed('stoi_bands'):
+        _lib.stoi_check(_lib.load_stoi().danet_stoi_bands(_lib.stream(), B, C, L10, ptr(sig), ptr(t['w']), ptr(t['tw']),
+                                                          ctypes.addressof(t['bands']), ptr(kidx), ptr(M), ptr(T)))
+    return T
+
+
+def stoi_segments(T, M, nf, out=None):
+    '''T [B, C, C + 2, 15, max(nf, 1)] and M [B, C] -> d float64 [B, C, C + 1, 2]: (STOI, ESTOI) of every reference
+    against every estimate and the mixture, ONE launch (danet_stoi_segments)'''
+    assert T.is_cuda and T.dtype == torch.float64 and T.dim() == 5 and T.is_contiguous()
+    B, C, dev = T.shape[0], T.shape[1], T.device
+    assert tuple(T.shape) == (B, C, C + 2, 15, max(int(nf), 1)), (T.shape, nf)
+    assert M.device == dev and M.dtype == torch.int32 and M.is_contiguous() and tuple(M.shape) == (B, C)
+    d = _bss_out(out, (B, C, C + 1, 2), torch.float64, dev)
+    with _lib.timed('stoi_segments'):
+        _lib.stoi_check(_lib.load_stoi().danet_stoi_segments(_lib.stream(), B, C, int(nf), ptr(T), ptr(M), ptr(d)))
+    return d
+
+
+def stoi_finalize(d, M, Emax, nf, b0=0, out=None):
+    '''d, M and Emax of B utterances -> (mean4 [4], per_utt [B_all, 4], perm_idx int32 [B_all], flags int32 [B_all],
+    count int32 [1]), ONE launch (danet_stoi_finalize): rows b0 .. b0 + B - 1 are written, and mean4 and count from
+    all rows when b0 + B = B_all.  out: optional (per_utt, perm_idx, flags, mean4, count) of a batch of B_all
+    utterances to write into (default B_all = B)'''
+    B, C, dev = d.shape[0], d.shape[1], d.device
+    for t_, shape, dtype in ((d, (B, C, C + 1, 2), torch.float64), (M, (B, C), torch.int32),
+                             (Emax, (B, C), torch.float64)):
+        assert t_.is_cuda and t_.device == dev and t_.dtype == dtype and t_.is_contiguous() \
+            and tuple(t_.shape) == shape, (t_.dtype, t_.shape, shape)
+    if out is None:
+        out = (torch.empty(B, 4, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.float64, device=dev),
+               torch.empty(1, dtype=torch.int32, device=dev))
+    per_utt, perm_idx, flags, mean4, count = out
+    B_all = per_utt.shape[0]
+    assert per_utt.dtype == torch.float64 and per_utt.is_contiguous() and tuple(per_utt.shape) == (B_all, 4)
+    assert perm_idx.dtype == torch.int32 and perm_idx.is_contiguous() and tuple(perm_idx.shape) == (B_all,)
+    assert flags.dtype == torch.int32 and flags.is_contiguous() and tuple(flags.shape) == (B_all,)
+    assert mean4.dtype == torch.float64 and mean4.is_contiguous() and mean4.numel() == 4
+    assert count.dtype == torch.int32 and count.numel() == 1
+    with _lib.timed('stoi_finalize'):
+        _lib.stoi_check(_lib.load_stoi().danet_stoi_finalize(
+            _lib.stream(), B, C, int(nf), ptr(d), ptr(M), ptr(Emax), int(b0), B_all, ptr(per_utt), ptr(perm_idx),
+            ptr(flags), ptr(mean4), ptr(count)))
+    return mean4, per_utt, perm_idx, flags, count
+
+
+def stoi_group(B, C, Ls, U, D):
+    '''the utterances ops.stoi_eval takes at a time: the most whose scratch stays under STOI_SCRATCH_BYTES (one at
+    least)'''
+    g = max(1, min(int(B), STOI_SCRATCH_BYTES // stoi_workspace_bytes(1, C, Ls, U, D)))
+    while g > 1 and stoi_workspace_bytes(g, C, Ls, U, D) > STOI_SCRATCH_BYTES:
+        g -= 1
+    return g
+
+
+def stoi_eval(src, est, fft_stride=None, wav=None, smprate=None, group=None, with_count=False):
+    '''STOI, ESTOI and their improvements over the mixture (the rule of include/danet_stoi_hip.h) of the waveforms of
+    the UNPERMUTED estimates `est` against the references `src`, both complex64 [B, C, T, F] -> (stoi, estoi, stoii,
+    estoii, per_utt [B, 4], perm_idx [B], flags [B]): float64 / int32 device tensors of the caller's own; with_count:
+    an eighth, the int32 [1] count of the utterances behind the means.  wav: the float32 waveforms
+    [B, 2C, (T - 1) * S] when they exist already (ops.si_sdr_wav), else they are synthesised here (ops.metric_synth,
+    into the metric's cached scratch).  smprate: default hparams.SMPRATE.  The utterances go through the stages in
+    groups of `group` (default ops.stoi_group); the batch means are formed on the device over all groups by the last
+    group's finalize launch, so they do not depend on the grouping.  Six launches a group, no host synchronisation.'''
+    B, C, T, F = src.shape
+    dev = src.device
+    if wav is None:
+        wav = synth_wav(src, est, fft_stride)
+    assert wav.is_cuda and wav.dtype == torch.float32 and wav.is_contiguous() and tuple(wav.shape[:2]) == (B, 2 * C)
+    smprate = _stoi_smprate(smprate)
+    t = stoi_tables(smprate, dev)
+    U, D, Ls = t['U'], t['D'], wav.shape[2]
+    nf = stoi_lengths(Ls, U, D)[1]
+    g = stoi_group(B, C, Ls, U, D) if group is None else max(1, min(int(group), B))
+    out = (torch.empty(B, 4, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+           torch.empty(B, dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.float64, device=dev),
+           torch.empty(1, dtype=torch.int32, device=dev))
+    for b0 in range(0, B, g):
+        nb = min(g, B - b0)
+        w = _stoi_workspace(nb, C, Ls, U, D, dev)
+        stoi_resample(wav[b0:b0 + nb], smprate, out=w['sig'])
+        stoi_frames(w['sig'], smprate, out=(w['E'], w['mask'], w['kidx'], w['M'], w['Emax']))
+        stoi_bands(w['sig'], w['kidx'], w['M'], smprate, out=w['T'])
+        stoi_segments(w['T'], w['M'], nf, out=w['d'])
+        stoi_finalize(w['d'], w['M'], w['Emax'], nf, b0=b0, out=out)
+    per_utt, perm_idx, flags, mean4, count = out
+    res = (mean4[0], mean4[1], mean4[2], mean4[3], per_utt, perm_idx, flags)
+    return res + (count,) if with_count else res
 
 
 # ---- waveform metric of a noisy valid / test sweep (include/danet_neval_hip.h) -------------------------
