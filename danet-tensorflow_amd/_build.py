@@ -1,5 +1,5 @@
 '''
-Builds the seventeen HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the eighteen HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -23,6 +23,7 @@ Builds the seventeen HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_stitch_hip.so        csrc/stitch/*.hip        include/danet_stitch_hip.h, csrc/ext_core.h
     libdanet_bss_hip.so           csrc/bss/*.hip           include/danet_bss_hip.h, csrc/ext_core.h
     libdanet_stoi_hip.so          csrc/stoi/*.hip          include/danet_stoi_hip.h, csrc/ext_core.h
+    libdanet_phase_hip.so         csrc/phase/*.hip         include/danet_phase_hip.h, csrc/{ext_core,wave_metric}.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -90,7 +91,8 @@ EXTENSIONS = (METRIC, NOISE, LEVEL, WAVLOSS, GCLIP, DPCL, NEVAL)
 STITCH = _extension('stitch', *_shared('ext_core'))
 BSS = _extension('bss', *_shared('ext_core'))
 STOI = _extension('stoi', *_shared('ext_core'))
-MORE_EXTENSIONS = (STITCH, BSS, STOI)
+PHASE = _extension('phase', *_shared('ext_core', 'wave_metric'))
+MORE_EXTENSIONS = (STITCH, BSS, STOI, PHASE)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out
 LEVEL_LIB = LEVEL.out
@@ -101,6 +103,7 @@ NEVAL_LIB = NEVAL.out
 STITCH_LIB = STITCH.out
 BSS_LIB = BSS.out
 STOI_LIB = STOI.out
+PHASE_LIB = PHASE.out
 
 
 def _sources(src_dir):
@@ -232,6 +235,10 @@ def build_bss(force=False, verbose=True):
 
 def build_stoi(force=False, verbose=True):
     return _build_spec(STOI, force, verbose)
+
+
+def build_phase(force=False, verbose=True):
+    return _build_spec(PHASE, force, verbose)
 
 
 def build_variant(name, defs):

@@ -1,7 +1,7 @@
 '''
-ctypes binding of the seventeen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+ctypes binding of the eighteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
 libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip, dpcl, neval,
-stitch, bss and stoi extension libraries.  Each is described
+stitch, bss, stoi and phase extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES, EXTENSIONS or MORE_EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -279,8 +279,18 @@ STOI_PROTOTYPES = {
     'danet_stoi_finalize': (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_phase_hip.h
+PHASE_PROTOTYPES = {
+    'danet_phase_abi_version': (c_int, []),
+    'danet_phase_last_error': (ctypes.c_char_p, []),
+    'danet_phase_workspace_bytes': (c_sz, [c_int, c_int, c_int, c_int, c_int]),
+    'danet_phase_init': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p]),
+    'danet_phase_synth': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p]),
+    'danet_phase_project': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Seventeen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Eighteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -378,7 +388,12 @@ BSS = Library('bss', 'libdanet_bss_hip.so', 'BSS_LIB_PATH', '_bss', BSS_PROTOTYP
 STOI_ABI_VERSION = 1
 STOI = Library('stoi', 'libdanet_stoi_hip.so', 'STOI_LIB_PATH', '_stoi', STOI_PROTOTYPES,
                STOI_ABI_VERSION, 'danet_stoi_', 'EVAL_STOI needs the HIP extension library')
-MORE_EXTENSIONS = (STITCH, BSS, STOI)
+# loaded at the first infer / valid step of a model built with PHASE_REFINE_ITERS set only (ops.phase_refine): a run
+# with the key null never maps it
+PHASE_ABI_VERSION = 1
+PHASE = Library('phase', 'libdanet_phase_hip.so', 'PHASE_LIB_PATH', '_phase', PHASE_PROTOTYPES,
+                PHASE_ABI_VERSION, 'danet_phase_', 'PHASE_REFINE_ITERS needs the HIP extension library')
+MORE_EXTENSIONS = (STITCH, BSS, STOI, PHASE)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -398,8 +413,9 @@ NEVAL_LIB_PATH = os.path.join(_CSRC, NEVAL.so)
 STITCH_LIB_PATH = os.path.join(_CSRC, STITCH.so)
 BSS_LIB_PATH = os.path.join(_CSRC, BSS.so)
 STOI_LIB_PATH = os.path.join(_CSRC, STOI.so)
+PHASE_LIB_PATH = os.path.join(_CSRC, PHASE.so)
 _lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = _gclip = _dpcl = None
-_neval = _stitch = _bss = _stoi = None
+_neval = _stitch = _bss = _stoi = _phase = None
 _lock = threading.Lock()
 
 
@@ -634,6 +650,17 @@ def load_stoi():
 def stoi_check(rc):
     if rc != 0:
         _check(STOI, rc)
+
+
+def load_phase():
+    if _phase is not None:
+        return _phase
+    return _load(PHASE)
+
+
+def phase_check(rc):
+    if rc != 0:
+        _check(PHASE, rc)
 
 
 # ---- switches ------------------------------------------------------------------

@@ -57,6 +57,10 @@ unchanged.  Differences, all deliberate:
   `STOI`, `ESTOI` and their improvements over the mixture `STOIi`, `ESTOIi` of the separated waveforms, for every
   dataset; it needs `SMPRATE` >= 8000 with a resampling table to 10 kHz of at most 16384 entries; not with
   `NOISE_EVAL_DIR`; `train_step`, `infer` and `debug_fetch` never compute them.
+* `PHASE_REFINE_ITERS` (an integer in 1..100, default None = off) makes `Model.infer` (chunked inference included) and
+  the waveform metrics of `Model.valid_step` run that many iterations of MISI phase refinement (multiple-input
+  spectrogram inversion) on the separated spectra, which otherwise carry the mixture's phase; `loss` and `SNR` stay
+  the figures of the unrefined output; not with `NOISE_EVAL_DIR`; `train_step` and `debug_fetch` never look at it.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -158,6 +162,9 @@ DEFAULTS = {
     # `valid` / `test` also report STOI, ESTOI and the improvement of each over the mixture, on the waveforms
     # resampled to 10 kHz: true = on, null / false = off (not in the reference; include/danet_stoi_hip.h)
     'EVAL_STOI': None,
+    # iterations of MISI phase refinement of the separated spectra in `infer` and ahead of the waveform metrics of
+    # `valid` / `test`: an integer in 1..100, None = off (not in the reference; include/danet_phase_hip.h)
+    'PHASE_REFINE_ITERS': None,
 }
 
 

@@ -78,6 +78,8 @@ class Model(object):
         # None: off; (L, V, G): chunk length, cross-fade and chunks per launch group of chunked inference (build() sets
         # it from INFER_CHUNK_LEN / INFER_CHUNK_OVERLAP / INFER_CHUNK_BATCH)
         self.infer_chunk = None
+        # None: off; an int: the iterations of MISI phase refinement (build() sets it from PHASE_REFINE_ITERS)
+        self.phase_refine = None
 
     # ------------------------------------------------------------ variables
     def get_variable(self, name, shape, init):
@@ -123,6 +125,8 @@ class Model(object):
         self.eval_bss = self._check_eval_bss()
         # STOI / ESTOI of the separated waveforms (include/danet_stoi_hip.h)
         self.eval_stoi = self._check_eval_stoi()
+        # None: off; an int: the iterations of MISI phase refinement (include/danet_phase_hip.h)
+        self.phase_refine = self._check_phase_refine()
         # 'pit-mse': the reference's PIT-MSE on complex spectra; 'si-sdr': -SI-SDR of the separated waveforms
         self.train_loss = self._check_train_loss()
         # None: off; a float: the largest global L2 norm of the gradient (include/danet_gclip_hip.h)
@@ -224,6 +228,21 @@ class Model(object):
         return True
 
     _stoi_key = _check_eval_stoi
+
+    @staticmethod
+    def _check_phase_refine():
+        '''PHASE_REFINE_ITERS (null: off) -> None or the iteration count; ValueError naming the key that rules it out'''
+        v = getattr(hparams, 'PHASE_REFINE_ITERS', None)
+        if v is None:
+            return None
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1 or v > 100:
+            raise ValueError('PHASE_REFINE_ITERS must be null or an integer in 1..100 (got %r)' % (v,))
+        if getattr(hparams, 'NOISE_EVAL_DIR', None) is not None:
+            raise ValueError('PHASE_REFINE_ITERS cannot be combined with NOISE_EVAL_DIR: the refined sources sum to the '
+                             'mixture, so the noise of a noisy mixture would be shared among them')
+        # the waveforms are those of danet_metric_synth: EVAL_SI_SDR's rules, under this key's name
+        Model._check_synth_envelope('PHASE_REFINE_ITERS', ops.PHASE_MAX_C)
+        return v
 
     @staticmethod
     def _check_train_loss():
@@ -674,13 +693,13 @@ class Model(object):
             wav = None
             if self.eval_si_sdr:
                 # the waveform metric does its own permutation search: the estimates go in unpermuted
-                est = ops.reattach_phase(out['sep_pwr_valid'], out['phasor'])
+                est = self._refined(ops.reattach_phase(out['sep_pwr_valid'], out['phasor']), s_src_signals)
                 if self.eval_bss is None and not self.eval_stoi:
                     res['SI-SDR'], res['SI-SDRi'] = ops.si_sdr(s_src_signals, est)[:2]
                 else:
                     res['SI-SDR'], res['SI-SDRi'], _, _, wav = ops.si_sdr_wav(s_src_signals, est)
             elif self.eval_bss is not None or self.eval_stoi:
-                est = ops.reattach_phase(out['sep_pwr_valid'], out['phasor'])
+                est = self._refined(ops.reattach_phase(out['sep_pwr_valid'], out['phasor']), s_src_signals)
                 if self.eval_bss is not None and self.eval_stoi:
                     # both read the waveforms: synthesised once, into the metric's cached scratch
                     wav = ops.synth_wav(s_src_signals, est)
@@ -693,10 +712,18 @@ class Model(object):
         ops.step_done(self.device, collective_consistent=not dist.is_dist())
         return res
 
+    def _refined(self, est, mixrows):
+        '''est complex64 [B, C, T, F] after PHASE_REFINE_ITERS iterations of MISI against the mixture that is the sum
+        of mixrows [B, Cm, T, F]; est itself with the key null'''
+        if self.phase_refine is None:
+            return est
+        return ops.phase_refine(est, mixrows, self.phase_refine)
+
     def infer(self, s_mixed_signals):
         '''`g_sess.run(infer_fetches, {s_mixed_signals: ...})` (main.py:384-385,
         685-690): complex mixture [B,T,F] -> separated complex [B,C,T,F] using
-        the inference estimator and the mixture phase (main.py:333-335).'''
+        the inference estimator and the mixture phase (main.py:333-335); with PHASE_REFINE_ITERS set, that phase
+        refined by ops.phase_refine.'''
         if self.infer_chunk is not None:
             if s_mixed_signals.shape[0] != 1:
                 raise ValueError('INFER_CHUNK_LEN is set: infer takes one recording at a time (got a batch of %d)'
@@ -710,7 +737,7 @@ class Model(object):
             s_embed = self.encoder(fe['mix_log'])
             s_attr = self.valid_estimator(s_embed, s_mix_pwr=fe['mix_pwr'])
             s_sep = self.separator(fe['mix_pwr'], s_attr, s_embed.reshape(B, -1, E))
-            res = ops.reattach_phase(s_sep, fe['phasor'])
+            res = self._refined(ops.reattach_phase(s_sep, fe['phasor']), s_mixed_signals[:, None])
         ops.step_done(self.device, collective_consistent=not dist.is_dist())
         return res
 
@@ -752,7 +779,8 @@ class Model(object):
         starts = ops.stitch_plan(T, L, V)
         s_chunks = torch.stack([s_mixed_signals[0, s:s + L] for s in starts])
         mags, phasor = self.infer_chunks(s_chunks)
-        return ops.stitch(mags, phasor, T, V)[None]
+        # the stitched recording is refined as a whole, against the whole mixture: T frames, one call
+        return self._refined(ops.stitch(mags, phasor, T, V)[None], s_mixed_signals[:, None])
 
     # ------------------------------------------------------- misc (main.py)
     def set_learn_rate(self, lr):

@@ -949,6 +949,120 @@ def synth_wav(src, est, fft_stride=None):
     return metric_synth(src, est, S, out=wav)
 
 
+# ---- MISI phase refinement of the separated spectra (include/danet_phase_hip.h) ---------------------------
+# On the extension library libdanet_phase_hip.so, mapped at the first call: a run with PHASE_REFINE_ITERS null never
+# gets here.  init (two launches), then per iteration: waveforms of the iterate -> projection onto the magnitudes.
+PHASE_MAX_C = 4                                      # DANET_PHASE_MAX_C
+_phase_ws = {}           # (device index, stream, B, C, T, N, S) -> the workspace buffer
+
+
+def phase_workspace_bytes(B, C, T, N, S):
+    '''danet_phase_workspace_bytes'''
+    return _lib.bytes_or_raise(_lib.load_phase().danet_phase_workspace_bytes(int(B), int(C), int(T), int(N), int(S)),
+                               _lib.phase_check)
+
+
+def phase_parts(ws, B, C, T, N, S):
+    '''(A float32 [B, C, T, F], mix complex64 [B, T, F], wav float32 [B, C + 1, Ls]): views of the three parts of a
+    workspace buffer (uint8, at least phase_workspace_bytes long) in the header's layout'''
+    F, Ls = N // 2 + 1, (T - 1) * S
+    views, off = [], 0
+    for shape, dtype, size in (((B, C, T, F), torch.float32, 4), ((B, T, F), torch.complex64, 8),
+                               ((B, C + 1, Ls), torch.float32, 4)):
+        n = int(np.prod(shape)) * size
+        views.append(ws[off:off + n].view(dtype).view(shape))
+        off += (n + 255) & ~255
+    return tuple(views)
+
+
+def _phase_workspace(B, C, T, N, S, dev):
+    '''the grow-only scratch 'phase' of this (device, stream), at least one workspace of this shape long; its size
+    is asked of the library once per shape'''
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
+           torch.cuda.current_stream().cuda_stream, B, C, T, N, S)
+    hit = _phase_ws.get(key)
+    if hit is not None and _lib._ws.get(key[:2] + ('phase',)) is hit:
+        return hit
+    if len(_phase_ws) >= 64:
+        _phase_ws.clear()
+    hit = _phase_ws[key] = _lib.workspace(phase_workspace_bytes(B, C, T, N, S), dev, 'phase')
+    return hit
+
+
+def _phase_args(x, window, ws, fft_stride):
+    assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 4 and x.is_contiguous(), (x.dtype, x.shape)
+    B, C, T, F = x.shape
+    N = 2 * (F - 1)
+    assert window.is_cuda and window.dtype == torch.float32 and window.is_contiguous() and window.numel() == N \
+        and window.device == x.device, (window.shape, N)
+    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == x.device
+    S = int(fft_stride)
+    assert ws.numel() >= phase_workspace_bytes(B, C, T, N, S), ws.numel()
+    return B, C, T, N, S
+
+
+def phase_init(est0, mixrows, window, ws, fft_stride, x=None):
+    '''danet_phase_init, TWO launches: A = |est0|, the mixture sum of mixrows [B, Cm, T, F] and y = synth(mixture) into
+    the workspace `ws`, and x = est0 (a fresh tensor unless given; x may be est0) -> x'''
+    if x is None:
+        x = torch.empty_like(est0)
+    B, C, T, N, S = _phase_args(x, window, ws, fft_stride)
+    assert est0.is_cuda and est0.dtype == torch.complex64 and est0.is_contiguous() and est0.shape == x.shape \
+        and est0.device == x.device, (est0.dtype, est0.shape)
+    assert mixrows.is_cuda and mixrows.dtype == torch.complex64 and mixrows.dim() == 4 and mixrows.is_contiguous() \
+        and mixrows.device == x.device and (mixrows.shape[0],) + tuple(mixrows.shape[2:]) == (B, T, N // 2 + 1), \
+        (mixrows.dtype, mixrows.shape)
+    with _lib.timed('phase_init'):
+        _lib.phase_check(_lib.load_phase().danet_phase_init(
+            _lib.stream(), B, C, mixrows.shape[1], T, N, S, ptr(torch.view_as_real(est0)),
+            ptr(torch.view_as_real(mixrows)), ptr(window), ptr(ws), ptr(torch.view_as_real(x))))
+    return x
+
+
+def phase_synth(x, window, ws, fft_stride):
+    '''danet_phase_synth, ONE launch: the waveforms of the C rows of every utterance of x into the workspace'''
+    B, C, T, N, S = _phase_args(x, window, ws, fft_stride)
+    with _lib.timed('phase_synth'):
+        _lib.phase_check(_lib.load_phase().danet_phase_synth(
+            _lib.stream(), B, C, T, N, S, ptr(torch.view_as_real(x)), ptr(window), ptr(ws)))
+
+
+def phase_project(x, window, ws, fft_stride, z_out=None):
+    '''danet_phase_project, ONE launch: redistribution, analysis and projection onto the magnitudes, x updated IN
+    PLACE; z_out (complex64, the shape of x) receives the analysis Z when given -> x'''
+    B, C, T, N, S = _phase_args(x, window, ws, fft_stride)
+    if z_out is not None:
+        assert z_out.is_cuda and z_out.dtype == torch.complex64 and z_out.is_contiguous() and z_out.shape == x.shape \
+            and z_out.device == x.device and z_out.data_ptr() != x.data_ptr(), (z_out.dtype, z_out.shape)
+    with _lib.timed('phase_project'):
+        _lib.phase_check(_lib.load_phase().danet_phase_project(
+            _lib.stream(), B, C, T, N, S, ptr(window), ptr(ws), ptr(torch.view_as_real(x)),
+            ptr(torch.view_as_real(z_out)) if z_out is not None else None))
+    return x
+
+
+def phase_refine(est0, mixrows, K, fft_stride=None, window=None):
+    '''K iterations of MISI on est0 complex64 [B, C, T, F] against the mixture that is the sum of mixrows complex64
+    [B, Cm, T, F] -> complex64 [B, C, T, F], a FRESH tensor with the magnitudes of est0 (K = 0: est0 bit for bit).
+    The workspace is a scratch cached per shape; 2 + 2K launches and nothing else on the device, no host
+    synchronisation.  window: float32 device vector [N] (default hparams.FFT_WND, uploaded once).'''
+    from .hparams import hparams
+    S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
+    K = int(K)
+    assert K >= 0, K
+    assert est0.is_cuda and est0.dtype == torch.complex64 and est0.dim() == 4, (est0.dtype, est0.shape)
+    est0, mixrows = est0.contiguous(), mixrows.contiguous()
+    B, C, T, F = est0.shape
+    dev = est0.device
+    window = _metric_window(dev) if window is None else _f32(window).contiguous()
+    ws = _phase_workspace(B, C, T, 2 * (F - 1), S, dev)
+    x = phase_init(est0, mixrows, window, ws, S)
+    for _ in range(K):
+        phase_synth(x, window, ws, S)
+        phase_project(x, window, ws, S)
+    return x
+
+
 # ---- BSS-eval figures of valid / test (include/danet_bss_hip.h) ----------------------------------------
 # On the extension library libdanet_bss_hip.so, mapped at the first call: a run with EVAL_BSS_SDR null never gets
 # here.  waveforms (ops.metric_synth) -> lagged correlations -> block-Toeplitz systems -> two batched Cholesky
