@@ -1,7 +1,7 @@
 '''
-ctypes binding of the eighteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+ctypes binding of the nineteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
 libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip, dpcl, neval,
-stitch, bss, stoi and phase extension libraries.  Each is described
+stitch, bss, stoi, phase and online extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES, EXTENSIONS or MORE_EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -289,8 +289,19 @@ PHASE_PROTOTYPES = {
     'danet_phase_project': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_online_hip.h
+ONLINE_PROTOTYPES = {
+    'danet_online_abi_version': (c_int, []),
+    'danet_online_last_error': (ctypes.c_char_p, []),
+    'danet_online_state_bytes': (c_sz, [c_int, c_int]),
+    'danet_online_init': (c_int, [c_p, c_int, c_int, c_int, c_p, c_p]),
+    'danet_online_scan': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f64, c_int, c_i64, c_f64, c_p, c_p,
+                                  c_p, c_p]),
+    'danet_online_separate': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Eighteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Nineteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -393,7 +404,12 @@ STOI = Library('stoi', 'libdanet_stoi_hip.so', 'STOI_LIB_PATH', '_stoi', STOI_PR
 PHASE_ABI_VERSION = 1
 PHASE = Library('phase', 'libdanet_phase_hip.so', 'PHASE_LIB_PATH', '_phase', PHASE_PROTOTYPES,
                 PHASE_ABI_VERSION, 'danet_phase_', 'PHASE_REFINE_ITERS needs the HIP extension library')
-MORE_EXTENSIONS = (STITCH, BSS, STOI, PHASE)
+# loaded at the first infer / valid step of a model whose inference estimator is "online", on a recording longer than
+# the hold, only (ops.online_attractors / ops.online_separate): a run with any other estimator never maps it
+ONLINE_ABI_VERSION = 1
+ONLINE = Library('online', 'libdanet_online_hip.so', 'ONLINE_LIB_PATH', '_online', ONLINE_PROTOTYPES,
+                 ONLINE_ABI_VERSION, 'danet_online_', 'the "online" estimator needs the HIP extension library')
+MORE_EXTENSIONS = (STITCH, BSS, STOI, PHASE, ONLINE)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -414,8 +430,9 @@ STITCH_LIB_PATH = os.path.join(_CSRC, STITCH.so)
 BSS_LIB_PATH = os.path.join(_CSRC, BSS.so)
 STOI_LIB_PATH = os.path.join(_CSRC, STOI.so)
 PHASE_LIB_PATH = os.path.join(_CSRC, PHASE.so)
+ONLINE_LIB_PATH = os.path.join(_CSRC, ONLINE.so)
 _lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = _gclip = _dpcl = None
-_neval = _stitch = _bss = _stoi = _phase = None
+_neval = _stitch = _bss = _stoi = _phase = _online = None
 _lock = threading.Lock()
 
 
@@ -661,6 +678,17 @@ def load_phase():
 def phase_check(rc):
     if rc != 0:
         _check(PHASE, rc)
+
+
+def load_online():
+    if _online is not None:
+        return _online
+    return _load(ONLINE)
+
+
+def online_check(rc):
+    if rc != 0:
+        _check(ONLINE, rc)
 
 
 # ---- switches ------------------------------------------------------------------

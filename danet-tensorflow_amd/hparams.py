@@ -61,6 +61,12 @@ unchanged.  Differences, all deliberate:
   the waveform metrics of `Model.valid_step` run that many iterations of MISI phase refinement (multiple-input
   spectrogram inversion) on the separated spectra, which otherwise carry the mixture's phase; `loss` and `SNR` stay
   the figures of the unrefined output; not with `NOISE_EVAL_DIR`; `train_step` and `debug_fetch` never look at it.
+* `INFER_ESTIMATOR_METHOD = "online"` selects the online attractor estimator: attractors that are updated frame by
+  frame from the frames seen so far (include/danet_online_hip.h), causal in the embedding.  `ONLINE_INIT_FRAMES` (the
+  hold length T0 in frames, an integer >= 1, default None = 32 when that estimator is selected: a choice, not a tuned
+  value) and `ONLINE_MEMORY_FRAMES` (tau > 0 frames, the forgetting factor being lambda = exp(-1 / tau); default None
+  = lambda = 1, the running mean of everything seen) need it; not as `TRAIN_ESTIMATOR_METHOD` (it has no backward) and
+  not with `INFER_CHUNK_LEN`.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -165,6 +171,12 @@ DEFAULTS = {
     # iterations of MISI phase refinement of the separated spectra in `infer` and ahead of the waveform metrics of
     # `valid` / `test`: an integer in 1..100, None = off (not in the reference; include/danet_phase_hip.h)
     'PHASE_REFINE_ITERS': None,
+    # the "online" inference estimator (INFER_ESTIMATOR_METHOD = "online"): the hold length T0 in frames, an integer
+    # >= 1 (None = 32 when the estimator is selected; a choice, not tuned), and the memory tau > 0 in frames of the
+    # forgetting factor lambda = exp(-1 / tau) (None = lambda = 1, the running mean of everything seen); both need that
+    # estimator (not in the reference; include/danet_online_hip.h)
+    'ONLINE_INIT_FRAMES': None,
+    'ONLINE_MEMORY_FRAMES': None,
 }
 
 

@@ -80,6 +80,9 @@ class Model(object):
         self.infer_chunk = None
         # None: off; an int: the iterations of MISI phase refinement (build() sets it from PHASE_REFINE_ITERS)
         self.phase_refine = None
+        # None: the inference estimator is not "online"; (T0, lambda): its hold length in frames and its forgetting
+        # factor (build() sets it from ONLINE_INIT_FRAMES / ONLINE_MEMORY_FRAMES)
+        self.online = None
 
     # ------------------------------------------------------------ variables
     def get_variable(self, name, shape, init):
@@ -136,6 +139,8 @@ class Model(object):
         self.dpcl_weight = self._check_dpcl_weight()
         # None: off; (L, V, G) of chunked inference (include/danet_stitch_hip.h)
         self.infer_chunk = self._check_infer_chunk()
+        # None: off; (T0, lambda) of the "online" inference estimator (include/danet_online_hip.h)
+        self.online = self._check_online()
         self.encoder = hparams.get_encoder()(self, 'encoder')
         self.estimator = hparams.get_estimator(
             hparams.TRAIN_ESTIMATOR_METHOD)(self, 'train_estimator')
@@ -330,6 +335,51 @@ class Model(object):
             raise ValueError('INFER_CHUNK_LEN needs MAX_N_SIGNAL <= %d (got %d): the stitching searches at most 24 '
                              'permutations per pair of chunks' % (ops.STITCH_MAX_C, hparams.MAX_N_SIGNAL))
         return L, V, 16 if G is None else G
+
+    @staticmethod
+    def _check_online():
+        '''INFER_ESTIMATOR_METHOD = "online" with ONLINE_INIT_FRAMES / ONLINE_MEMORY_FRAMES -> None (another estimator)
+        or (T0, lambda), lambda = exp(-1 / ONLINE_MEMORY_FRAMES) formed in float64; ValueError naming the keys that rule
+        the choice out'''
+        t0 = getattr(hparams, 'ONLINE_INIT_FRAMES', None)
+        tau = getattr(hparams, 'ONLINE_MEMORY_FRAMES', None)
+        if t0 is not None and (isinstance(t0, bool) or not isinstance(t0, int) or t0 < 1):
+            raise ValueError('ONLINE_INIT_FRAMES must be null or an integer >= 1 (got %r)' % (t0,))
+        if tau is not None and (isinstance(tau, bool) or not isinstance(tau, (int, float)) or not math.isfinite(tau)
+                                or tau <= 0):
+            raise ValueError('ONLINE_MEMORY_FRAMES must be null or a finite number > 0 (got %r)' % (tau,))
+        if hparams.TRAIN_ESTIMATOR_METHOD == 'online':
+            raise ValueError('TRAIN_ESTIMATOR_METHOD cannot be "online": the online estimator has no backward, it is an '
+                             'inference estimator (INFER_ESTIMATOR_METHOD)')
+        if hparams.INFER_ESTIMATOR_METHOD != 'online':
+            for key, v in (('ONLINE_INIT_FRAMES', t0), ('ONLINE_MEMORY_FRAMES', tau)):
+                if v is not None:
+                    raise ValueError('%s is set (%r) while INFER_ESTIMATOR_METHOD is %r: it needs INFER_ESTIMATOR_METHOD '
+                                     '= "online"' % (key, v, hparams.INFER_ESTIMATOR_METHOD))
+            return None
+        if getattr(hparams.get_separator(hparams.SEPARATOR_TYPE), 'ACT', None) is None:
+            raise ValueError('INFER_ESTIMATOR_METHOD = "online" needs a separator that exposes its activation (ACT, the '
+                             'dot-product separators); SEPARATOR_TYPE = %r does not' % (hparams.SEPARATOR_TYPE,))
+        if getattr(hparams, 'INFER_CHUNK_LEN', None) is not None:
+            raise ValueError('INFER_ESTIMATOR_METHOD = "online" cannot be combined with INFER_CHUNK_LEN: every chunk '
+                             'would restart the track')
+        for key, v, most in (('MAX_N_SIGNAL', hparams.MAX_N_SIGNAL, ops.ONLINE_MAX_C),
+                             ('EMBED_SIZE', hparams.EMBED_SIZE, ops.ONLINE_MAX_E),
+                             ('FFT_SIZE', hparams.FFT_SIZE, 2 * (ops.ONLINE_MAX_F - 1))):
+            if v > most:
+                raise ValueError('INFER_ESTIMATOR_METHOD = "online" needs %s <= %d (got %d)' % (key, most, v))
+        lam = 1.0 if tau is None else math.exp(-1.0 / float(tau))
+        if not lam > 0.0:
+            raise ValueError('ONLINE_MEMORY_FRAMES = %r is too small: exp(-1 / tau) underflows to 0' % (tau,))
+        return (32 if t0 is None else t0), lam
+
+    def _separate(self, s_mix_pwr, s_attractors, s_embed_flat):
+        '''the separated magnitudes [B, C, T, F] of the validation branch and of infer: a trajectory of attractors
+        [B, T, C, E] (the "online" estimator past its hold) goes to ops.online_separate, one attractor set [B, C, E] to
+        the separator as ever'''
+        if s_attractors.dim() == 4:
+            return ops.online_separate(s_mix_pwr, s_attractors, s_embed_flat, self.separator.ACT)
+        return self.separator(s_mix_pwr, s_attractors, s_embed_flat)
 
     def _flatten(self):
         n = sum(self.vars[k].numel() for k in self._order)
@@ -552,7 +602,7 @@ class Model(object):
                     # extra keyword the reference's estimator signature already has
                     # (app/modules.py:501), used by the k-means extension as weights
                     s_vattr = self.valid_estimator(s_embed, s_mix_pwr=fe['mix_pwr'])
-                s_vsep = self.separator(fe['mix_pwr'], s_vattr, s_embed_flat)  # :277-278
+                s_vsep = self._separate(fe['mix_pwr'], s_vattr, s_embed_flat)  # :277-278
             vloss, perms, vidx, vsnr = ops.pit_mse_loss(       # main.py:312-313, 336-337
                 s_src_signals, s_vsep, phasor, mode=1, eps=eps)
             out.update(valid_attrs=s_vattr, sep_pwr_valid=s_vsep, valid_loss=vloss,
@@ -736,7 +786,7 @@ class Model(object):
             fe = ops.frontend(s_mixed_signals[:, None].contiguous())
             s_embed = self.encoder(fe['mix_log'])
             s_attr = self.valid_estimator(s_embed, s_mix_pwr=fe['mix_pwr'])
-            s_sep = self.separator(fe['mix_pwr'], s_attr, s_embed.reshape(B, -1, E))
+            s_sep = self._separate(fe['mix_pwr'], s_attr, s_embed.reshape(B, -1, E))
             res = self._refined(ops.reattach_phase(s_sep, fe['phasor']), s_mixed_signals[:, None])
         ops.step_done(self.device, collective_consistent=not dist.is_dist())
         return res

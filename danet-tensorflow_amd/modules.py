@@ -353,6 +353,44 @@ class KMeansEstimator(Estimator):
         return s_attr
 
 
+@hparams.register_estimator('online')
+class OnlineEstimator(Estimator):
+    '''attractors updated frame by frame from the frames seen so far, after the Online Deep Attractor Network (Han,
+    Wang, Luo, Mesgarani 2019) -- include/danet_online_hip.h.  NOT in the reference; an inference estimator with no
+    backward.  The first T0 = ONLINE_INIT_FRAMES frames are the hold: the anchor estimator (the same `anchors` variable,
+    name and shape, so the parameter files of `anchor` / `kmeans` load) gives A0 from them, and from frame T0 on every
+    frame's attractors are the |mix|-weighted, soft-assigned means of the frames up to it, with the forgetting factor
+    lambda = exp(-1 / ONLINE_MEMORY_FRAMES).  Returns the trajectory [B, T, C, E] (Model._separate sends it to
+    ops.online_separate), or for a recording no longer than the hold the anchor estimator's [B, C, E], bit for bit.
+    Causal in the embedding; the encoders are not causal, so this alone is not streaming.'''
+    USE_TRUTH = False
+
+    def __init__(self, model, name):
+        super(OnlineEstimator, self).__init__(model, name)
+        self.name = name
+
+    def __call__(self, s_embed, s_src_pwr=None, s_mix_pwr=None, s_embed_flat=None):
+        B, T, F, E = s_embed.shape
+        C = hparams.MAX_N_SIGNAL
+        T0, lam = self.model.online
+        v_anchors = self.model.get_variable(
+            self.name + '/anchors', [hparams.NUM_ANCHOR, hparams.EMBED_SIZE],
+            lambda shape, gen: torch.randn(shape, generator=gen, dtype=torch.float64).float())
+        s_a0, _, _ = ops.AnchorAttractorFn.apply(s_embed[:, :min(T0, T)].contiguous(), v_anchors, C)
+        if hparams.DEBUG:
+            self.debug_fetches = dict(anchors=v_anchors)
+        if T <= T0:
+            return s_a0                                      # [B, C, E]: the plain separator runs
+        with torch.no_grad():
+            if s_mix_pwr is None:
+                s_mix_pwr = torch.ones(B, T, F, device=s_embed.device)
+            s_traj = ops.online_attractors(s_embed.detach(), s_mix_pwr, s_a0.detach(), self.model.separator.ACT, lam, T0,
+                                           float(hparams.EPS))
+        if hparams.DEBUG:
+            self.debug_fetches['attr_trajectory'] = s_traj
+        return s_traj                                        # [B, T, C, E]
+
+
 class _DotSeparatorBase(Separator):
     ACT = None
 

@@ -1063,6 +1063,85 @@ def phase_refine(est0, mixrows, K, fft_stride=None, window=None):
     return x
 
 
+# ---- the online attractor estimator (include/danet_online_hip.h) ----------------------------------------------
+# On the extension library libdanet_online_hip.so, mapped at the first call: a run with another inference estimator
+# never gets here.  init (one launch) -> scan (one launch, one workgroup per utterance) -> separate (one launch).
+ONLINE_MAX_C = 4                                     # DANET_ONLINE_MAX_C
+ONLINE_MAX_E = 64                                    # DANET_ONLINE_MAX_E
+ONLINE_MAX_F = 1025                                  # DANET_ONLINE_MAX_F
+ONLINE_MAX_T = 65536                                 # DANET_ONLINE_MAX_T
+
+
+def online_state_bytes(C, E):
+    '''danet_online_state_bytes: the bytes of ONE utterance's state, float64 S [C][E], n [C], A [C][E]'''
+    return _lib.bytes_or_raise(_lib.load_online().danet_online_state_bytes(int(C), int(E)), _lib.online_check)
+
+
+def online_state_parts(state, C, E):
+    '''(S [B, C, E], n [B, C], A [B, C, E]): views of a state tensor float64 [B, 2 C E + C] in the header's layout'''
+    B, CE = state.shape[0], C * E
+    assert state.dtype == torch.float64 and state.shape == (B, 2 * CE + C), (state.dtype, state.shape)
+    return state[:, :CE].view(B, C, E), state[:, CE:CE + C], state[:, CE + C:].view(B, C, E)
+
+
+def online_init(a0, state=None):
+    '''danet_online_init, ONE launch: a0 float32 [B, C, E] -> state float64 [B, 2 C E + C] with S = 0, n = 0, A = a0'''
+    assert a0.dim() == 3, a0.shape
+    a0 = _f32(a0.contiguous())
+    B, C, E = a0.shape
+    if state is None:
+        state = torch.empty(B, online_state_bytes(C, E) // 8, dtype=torch.float64, device=a0.device)
+    assert state.is_cuda and state.dtype == torch.float64 and state.is_contiguous() and state.device == a0.device \
+        and state.shape == (B, 2 * C * E + C), (state.dtype, state.shape)
+    with _lib.timed('online_init'):
+        _lib.online_check(_lib.load_online().danet_online_init(_lib.stream(), B, C, E, ptr(a0), ptr(state)))
+    return state
+
+
+def online_scan(embed, w, state, act, lam, T0, eps, t_first=0, attr=None):
+    '''danet_online_scan, ONE launch: the frames t_first .. t_first + T - 1 of embed float32 [B, T, F, E] with the
+    weights w float32 [B, T, F], from `state` (float64 [B, 2 C E + C], updated IN PLACE) -> the trajectory attr float32
+    [B, T, C, E]'''
+    assert embed.dim() == 4 and embed.is_contiguous() and w.is_contiguous(), (embed.shape, w.shape)
+    embed, w = _f32(embed), _f32(w)
+    B, T, F, E = embed.shape
+    assert tuple(w.shape) == (B, T, F) and w.device == embed.device, (w.shape, embed.shape)
+    assert state.is_cuda and state.dtype == torch.float64 and state.is_contiguous() and state.device == embed.device \
+        and state.dim() == 2 and state.shape[0] == B and (state.shape[1] % (2 * E + 1)) == 0, (state.dtype, state.shape)
+    C = state.shape[1] // (2 * E + 1)
+    if attr is None:
+        attr = torch.empty(B, T, C, E, device=embed.device)
+    assert _f32(attr).is_contiguous() and tuple(attr.shape) == (B, T, C, E) and attr.device == embed.device, attr.shape
+    with _lib.timed('online_scan'):
+        _lib.online_check(_lib.load_online().danet_online_scan(
+            _lib.stream(), B, C, T, F, E, int(act), float(lam), int(T0), int(t_first), float(eps), ptr(embed), ptr(w),
+            ptr(state), ptr(attr)))
+    return attr
+
+
+def online_separate(w, attr, embed, act, out=None):
+    '''danet_online_separate, ONE launch: out[b][c][t][f] = w[b][t][f] * act(embed[b][t][f] . attr[b][t][c]) with
+    w float32 [B, T, F], attr float32 [B, T, C, E], embed float32 [B, T, F, E] (or flat [B, T F, E]) -> [B, C, T, F]'''
+    w, attr, embed = _f32(w.contiguous()), _f32(attr.contiguous()), _f32(embed.contiguous())
+    B, T, F = w.shape
+    assert attr.dim() == 4 and tuple(attr.shape[:2]) == (B, T), (attr.shape, w.shape)
+    C, E = attr.shape[2], attr.shape[3]
+    assert embed.numel() == B * T * F * E and embed.shape[0] == B and embed.shape[-1] == E, (embed.shape, w.shape)
+    if out is None:
+        out = torch.empty(B, C, T, F, device=w.device)
+    assert _f32(out).is_contiguous() and tuple(out.shape) == (B, C, T, F) and out.device == w.device, out.shape
+    with _lib.timed('online_separate'):
+        _lib.online_check(_lib.load_online().danet_online_separate(
+            _lib.stream(), int(act), B, C, T, F, E, ptr(w), ptr(attr), ptr(embed), ptr(out)))
+    return out
+
+
+def online_attractors(embed, w, a0, act, lam, T0, eps):
+    '''init plus one scan: the trajectory attr float32 [B, T, C, E] of embed [B, T, F, E] with the weights w [B, T, F]
+    from the initial attractors a0 [B, C, E]; lam the forgetting factor, T0 the hold length in frames'''
+    return online_scan(embed.contiguous(), w.contiguous(), online_init(a0), act, lam, T0, eps)
+
+
 # ---- BSS-eval figures of valid / test (include/danet_bss_hip.h) ----------------------------------------
 # On the extension library libdanet_bss_hip.so, mapped at the first call: a run with EVAL_BSS_SDR null never gets
 # here.  waveforms (ops.metric_synth) -> lagged correlations -> block-Toeplitz systems -> two batched Cholesky
