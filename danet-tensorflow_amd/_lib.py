@@ -1,7 +1,7 @@
 '''
-ctypes binding of the nineteen HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+ctypes binding of the twenty HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
 libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip, dpcl, neval,
-stitch, bss, stoi, phase and online extension libraries.  Each is described
+stitch, bss, stoi, phase, online and causal extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES, EXTENSIONS or MORE_EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -300,8 +300,20 @@ ONLINE_PROTOTYPES = {
     'danet_online_separate': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_causal_hip.h
+CAUSAL_PROTOTYPES = {
+    'danet_causal_abi_version': (c_int, []),
+    'danet_causal_last_error': (ctypes.c_char_p, []),
+    'danet_causal_center_fwd': (c_int, [c_p, c_int, c_int, c_int, c_p, c_int, c_int, c_p, c_int, c_int, c_p]),
+    'danet_causal_center_bwd': (c_int, [c_p, c_int, c_int, c_int, c_p, c_int, c_int, c_p, c_int, c_int]),
+    'danet_causal_lstm_ws_bytes': (c_sz, [c_int, c_int, c_int, c_int]),
+    'danet_causal_lstm_block': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_int, ctypes.POINTER(c_p),
+                                        ctypes.POINTER(c_p), c_p, c_p, c_p, c_int, c_p, c_sz]),
+    'danet_causal_project': (c_int, [c_p, c_int, c_int, c_int, c_p, c_int, c_p, c_int, c_p, c_int]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Nineteen shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Twenty shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -409,7 +421,13 @@ PHASE = Library('phase', 'libdanet_phase_hip.so', 'PHASE_LIB_PATH', '_phase', PH
 ONLINE_ABI_VERSION = 1
 ONLINE = Library('online', 'libdanet_online_hip.so', 'ONLINE_LIB_PATH', '_online', ONLINE_PROTOTYPES,
                  ONLINE_ABI_VERSION, 'danet_online_', 'the "online" estimator needs the HIP extension library')
-MORE_EXTENSIONS = (STITCH, BSS, STOI, PHASE, ONLINE)
+# loaded at the first forward pass of the `lstm-causal` encoder or the first Model.open_stream only (ops.causal_*): a
+# run with another encoder and INFER_STREAM_BLOCK null never maps it
+CAUSAL_ABI_VERSION = 1
+CAUSAL = Library('causal', 'libdanet_causal_hip.so', 'CAUSAL_LIB_PATH', '_causal', CAUSAL_PROTOTYPES,
+                 CAUSAL_ABI_VERSION, 'danet_causal_', 'the lstm-causal encoder and streaming inference need the HIP '
+                 'extension library')
+MORE_EXTENSIONS = (STITCH, BSS, STOI, PHASE, ONLINE, CAUSAL)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -431,8 +449,9 @@ BSS_LIB_PATH = os.path.join(_CSRC, BSS.so)
 STOI_LIB_PATH = os.path.join(_CSRC, STOI.so)
 PHASE_LIB_PATH = os.path.join(_CSRC, PHASE.so)
 ONLINE_LIB_PATH = os.path.join(_CSRC, ONLINE.so)
+CAUSAL_LIB_PATH = os.path.join(_CSRC, CAUSAL.so)
 _lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = _gclip = _dpcl = None
-_neval = _stitch = _bss = _stoi = _phase = _online = None
+_neval = _stitch = _bss = _stoi = _phase = _online = _causal = None
 _lock = threading.Lock()
 
 
@@ -689,6 +708,17 @@ def load_online():
 def online_check(rc):
     if rc != 0:
         _check(ONLINE, rc)
+
+
+def load_causal():
+    if _causal is not None:
+        return _causal
+    return _load(CAUSAL)
+
+
+def causal_check(rc):
+    if rc != 0:
+        _check(CAUSAL, rc)
 
 
 # ---- switches ------------------------------------------------------------------

@@ -67,6 +67,14 @@ unchanged.  Differences, all deliberate:
   value) and `ONLINE_MEMORY_FRAMES` (tau > 0 frames, the forgetting factor being lambda = exp(-1 / tau); default None
   = lambda = 1, the running mean of everything seen) need it; not as `TRAIN_ESTIMATOR_METHOD` (it has no backward) and
   not with `INFER_CHUNK_LEN`.
+* `ENCODER_TYPE = "lstm-causal"` selects the causal encoder: the `lstm-orig` stack (same variables, so its parameter
+  files load) with both whole-utterance centrings replaced by a running mean over the frames seen so far
+  (include/danet_causal_hip.h); the embedding of frame t then depends on frames <= t only.  It trains like `lstm-orig`.
+  With it and `INFER_ESTIMATOR_METHOD = "online"`, `Model.open_stream(batch)` returns a session that separates a
+  recording block by block as it arrives, and `INFER_STREAM_BLOCK` (an integer in 1..64, default None = off) makes
+  `Model.infer` feed the recording through such a session in blocks of that many frames; it needs that encoder and
+  that estimator, `BATCH_SIZE` <= 16 when `infer` runs, and not `INFER_CHUNK_LEN` or `PHASE_REFINE_ITERS`;
+  `train_step` and `valid_step` never look at it.
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''
@@ -177,6 +185,10 @@ DEFAULTS = {
     # estimator (not in the reference; include/danet_online_hip.h)
     'ONLINE_INIT_FRAMES': None,
     'ONLINE_MEMORY_FRAMES': None,
+    # block-wise streaming inference: Model.infer feeds the recording through a Model.open_stream session in blocks of
+    # this many frames, an integer in 1..64, None = off; needs ENCODER_TYPE = "lstm-causal" and INFER_ESTIMATOR_METHOD
+    # = "online", not with INFER_CHUNK_LEN or PHASE_REFINE_ITERS (not in the reference; include/danet_causal_hip.h)
+    'INFER_STREAM_BLOCK': None,
 }
 
 

@@ -83,6 +83,9 @@ class Model(object):
         # None: the inference estimator is not "online"; (T0, lambda): its hold length in frames and its forgetting
         # factor (build() sets it from ONLINE_INIT_FRAMES / ONLINE_MEMORY_FRAMES)
         self.online = None
+        # None: off; an int: the frames per block Model.infer feeds through a stream session (build() sets it from
+        # INFER_STREAM_BLOCK)
+        self.stream_block = None
 
     # ------------------------------------------------------------ variables
     def get_variable(self, name, shape, init):
@@ -141,6 +144,9 @@ class Model(object):
         self.infer_chunk = self._check_infer_chunk()
         # None: off; (T0, lambda) of the "online" inference estimator (include/danet_online_hip.h)
         self.online = self._check_online()
+        # None: off; an int in 1..64: infer goes through a stream session in blocks of that many frames
+        # (include/danet_causal_hip.h)
+        self.stream_block = self._check_stream_block()
         self.encoder = hparams.get_encoder()(self, 'encoder')
         self.estimator = hparams.get_estimator(
             hparams.TRAIN_ESTIMATOR_METHOD)(self, 'train_estimator')
@@ -372,6 +378,40 @@ class Model(object):
         if not lam > 0.0:
             raise ValueError('ONLINE_MEMORY_FRAMES = %r is too small: exp(-1 / tau) underflows to 0' % (tau,))
         return (32 if t0 is None else t0), lam
+
+    @staticmethod
+    def _check_stream_block():
+        '''INFER_STREAM_BLOCK (null: off) -> None or the frames per block; ValueError naming the keys that rule it out'''
+        v = getattr(hparams, 'INFER_STREAM_BLOCK', None)
+        if v is None:
+            return None
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= ops.CAUSAL_MAX_TB:
+            raise ValueError('INFER_STREAM_BLOCK must be null or an integer in 1..%d (got %r)' % (ops.CAUSAL_MAX_TB, v))
+        Model._check_stream_model('INFER_STREAM_BLOCK')
+        for key in ('INFER_CHUNK_LEN', 'PHASE_REFINE_ITERS'):
+            if getattr(hparams, key, None) is not None:
+                raise ValueError('INFER_STREAM_BLOCK cannot be combined with %s: a stream session decides every frame '
+                                 'when it arrives, and both of them need the whole recording' % key)
+        return v
+
+    @staticmethod
+    def _check_stream_model(who):
+        '''what a stream session needs of the configuration; ValueError naming `who` and the key in its way'''
+        if hparams.ENCODER_TYPE != 'lstm-causal':
+            raise ValueError('%s needs ENCODER_TYPE = "lstm-causal" (got %r): the other encoders see the whole '
+                             'recording' % (who, hparams.ENCODER_TYPE))
+        if hparams.INFER_ESTIMATOR_METHOD != 'online':
+            raise ValueError('%s needs INFER_ESTIMATOR_METHOD = "online" (got %r): the other estimators form one '
+                             'attractor set from the whole recording' % (who, hparams.INFER_ESTIMATOR_METHOD))
+        if getattr(hparams.get_separator(hparams.SEPARATOR_TYPE), 'ACT', None) is None:
+            raise ValueError('%s needs a separator that exposes its activation (ACT, the dot-product separators); '
+                             'SEPARATOR_TYPE = %r does not' % (who, hparams.SEPARATOR_TYPE))
+
+    def open_stream(self, batch=1):
+        '''a SeparationStream over `batch` recordings that arrive block by block (ENCODER_TYPE = "lstm-causal",
+        INFER_ESTIMATOR_METHOD = "online", a dot-product separator, batch <= 16; anything else is a ValueError that names
+        the key)'''
+        return SeparationStream(self, batch)
 
     def _separate(self, s_mix_pwr, s_attractors, s_embed_flat):
         '''the separated magnitudes [B, C, T, F] of the validation branch and of infer: a trajectory of attractors
@@ -774,6 +814,8 @@ class Model(object):
         685-690): complex mixture [B,T,F] -> separated complex [B,C,T,F] using
         the inference estimator and the mixture phase (main.py:333-335); with PHASE_REFINE_ITERS set, that phase
         refined by ops.phase_refine.'''
+        if self.stream_block is not None:
+            return self._infer_stream(s_mixed_signals)
         if self.infer_chunk is not None:
             if s_mixed_signals.shape[0] != 1:
                 raise ValueError('INFER_CHUNK_LEN is set: infer takes one recording at a time (got a batch of %d)'
@@ -790,6 +832,20 @@ class Model(object):
             res = self._refined(ops.reattach_phase(s_sep, fe['phasor']), s_mixed_signals[:, None])
         ops.step_done(self.device, collective_consistent=not dist.is_dist())
         return res
+
+    def _infer_stream(self, s_mixed_signals):
+        '''infer with INFER_STREAM_BLOCK = n: the recording goes through a stream session in blocks of n frames and the
+        separated blocks are concatenated; bit for bit what any other block size gives'''
+        if hparams.BATCH_SIZE > ops.CAUSAL_MAX_B:
+            raise ValueError('INFER_STREAM_BLOCK needs BATCH_SIZE <= %d when infer runs (got %d)'
+                             % (ops.CAUSAL_MAX_B, hparams.BATCH_SIZE))
+        n, T = self.stream_block, s_mixed_signals.shape[1]
+        ops.poll_status(self.device)
+        stream = self.open_stream(s_mixed_signals.shape[0])
+        parts = [stream.push(s_mixed_signals[:, t:t + n]) for t in range(0, T, n)]
+        parts.append(stream.flush())
+        ops.step_done(self.device, collective_consistent=not dist.is_dist())
+        return torch.cat(parts, dim=2)
 
     def infer_chunks(self, s_chunks):
         '''the chunks of one recording, complex64 [n, L, F] -> (mags float32 [n, C, L, F], phasor float32
@@ -902,3 +958,140 @@ class Model(object):
 
     def grad_dict(self):
         return {k: v.grad.detach().cpu().numpy() for k, v in self.vars.items()}
+
+
+class SeparationStream(object):
+    '''Block-wise streaming inference (Model.open_stream): push(frames) takes the next frames of `batch` recordings,
+    complex64 [batch, n, F], and returns the separated frames the call decided, complex64 [batch, C, m, F].  The
+    session owns everything that travels from block to block -- the two centring states, the LSTM layers' h and c, the
+    online estimator's state and the absolute frame index -- and runs each block of at most 64 frames through
+    ops.frontend, the causal centring, ops.causal_lstm_block, the causal centring, ops.causal_project, ops.online_scan,
+    ops.online_separate and ops.reattach_phase (include/danet_causal_hip.h, include/danet_online_hip.h).  Every one of
+    them gives a frame the same bits whatever block it arrives in, so the concatenated output does not depend on how
+    the recording was cut.
+
+    Until T0 = ONLINE_INIT_FRAMES frames have arrived their embedding and |mix| are kept and push returns zero
+    frames (the online estimator forms A0 from the first T0 frames); the call that brings frame T0 - 1 returns every
+    frame so far.  flush() ends the recording: past the hold it has nothing left to return; on a recording no longer
+    than the hold it returns what Model.infer returns there, the plain separator with A0 of the frames there are.
+    reset() starts the next recording.  The STFT is per frame and stays with the caller, as with Model.infer.'''
+
+    BLOCK = ops.CAUSAL_MAX_TB
+
+    def __init__(self, model, batch=1):
+        Model._check_stream_model('open_stream')
+        if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= ops.CAUSAL_MAX_B:
+            raise ValueError('open_stream: batch must be an integer in 1..%d (got %r); BATCH_SIZE recordings at most '
+                             'that many go through one session' % (ops.CAUSAL_MAX_B, batch))
+        if not model.built or model.online is None:
+            raise ValueError('open_stream needs a built model with INFER_ESTIMATOR_METHOD = "online"')
+        self.model, self.batch = model, batch
+        H, L = model.encoder._dims()
+        if H % 4 or H > ops.CAUSAL_MAX_H or L > ops.CAUSAL_MAX_L or hparams.FEATURE_SIZE > ops.CAUSAL_MAX_D0:
+            raise ValueError('open_stream needs LSTM_HDIM a multiple of 4 and <= %d, NUM_LSTM_LAYERS <= %d and FFT_SIZE '
+                             '<= %d (got %d, %d, %d)' % (ops.CAUSAL_MAX_H, ops.CAUSAL_MAX_L,
+                                                         2 * (ops.CAUSAL_MAX_D0 - 1), H, L, hparams.FFT_SIZE))
+        self.H, self.L = H, L
+        enc = 'global/' + model.encoder.name
+        # (views into the model's flat parameter buffer.  danet_causal_lstm_block wants W[l] 16-byte aligned: they are,
+        # because the encoder's variables come first in that buffer and each holds a multiple of 4 floats when H % 4 == 0;
+        # a layout that broke this would be refused by the library with a message, not read misaligned)
+        self.Ws =[model.vars['%s/lstm%d/LSTM/linear/W' % (enc, l)].detach() for l in range(L)]
+        self.bs = [model.vars['%s/lstm%d/LSTM/linear/B' % (enc, l)].detach() for l in range(L)]
+        self.Wout = model.vars[enc + '/output/W'].detach()
+        self.anchors = model.vars['global/%s/anchors' % model.valid_estimator.name].detach()
+        dev = model.device
+        self.h = torch.empty(L, batch, H, device=dev)
+        self.c = torch.empty(L, batch, H, device=dev)
+        self.center_in = ops.causal_center_state(batch, dev)
+        self.center_top = ops.causal_center_state(batch, dev)
+        # what a block needs between its launches, owned here and sized for BLOCK frames so that push allocates only
+        # what it returns or keeps: the centred input, the top layer's output, its centred copy, the block kernel's
+        # workspace.  Every launch is ordered on the stream, so the next block may overwrite them.
+        self.Fp = (hparams.FEATURE_SIZE + 3) // 4 * 4
+        self.xc = torch.empty(self.BLOCK * batch * self.Fp, device=dev)
+        self.y = torch.empty(self.BLOCK * batch * H, device=dev)
+        self.yc = torch.empty(self.BLOCK * batch * H, device=dev)
+        self.ws = torch.empty(ops.causal_lstm_ws_bytes(L, batch, self.BLOCK, H) // 4, device=dev)
+        # the embedding [batch, n, F, E] of the last block and the attractors [batch, m, C, E] of the last frames
+        # decided (tests and tools)
+        self.embed = self.attr = None
+        self.reset()
+
+    def reset(self):
+        '''forget the recording: zero state, frame index 0'''
+        for t in (self.h, self.c, self.center_in, self.center_top):
+            t.zero_()
+        self.t = 0                   # the absolute index of the next frame
+        self.state = None            # the online estimator's state, float64 [batch, 2 C E + C], once A0 exists
+        self.held = []               # (embed, mix_pwr, phasor) of the blocks of the hold
+
+    def _encode(self, frames):
+        '''the next n <= 64 frames -> (embed [batch, n, F, E], mix_pwr [batch, n, F], phasor [batch, n, F, 2])'''
+        B, n, F = frames.shape
+        E, H, Fp = hparams.EMBED_SIZE, self.H, self.Fp
+        fe = ops.frontend(frames[:, None].contiguous())
+        xc = self.xc[:n * B * Fp].view(n, B, Fp)
+        y = self.y[:n * B * H].view(n, B, H)
+        yc = self.yc[:B * n * H].view(B, n, H)
+        ops.causal_center_fwd(fe['mix_log'], B, n, F, 0, F, xc, 1, Fp, self.center_in)
+        ops.causal_lstm_block(xc, Fp, F, self.Ws, self.bs, self.h, self.c, y=y, ldy=H, ws=self.ws)
+        ops.causal_center_fwd(y, B, n, H, 1, H, yc, 0, H, self.center_top)
+        embed = ops.causal_project(yc, B * n, H, F * E, H, self.Wout, F * E).view(B, n, F, E)
+        return embed, fe['mix_pwr'], fe['phasor']
+
+    def _track(self, embed, w, phasor, t_first):
+        '''the online estimator over the frames t_first .. of the recording, from the carried state'''
+        m = self.model
+        T0, lam = m.online
+        attr = ops.online_scan(embed, w, self.state, m.separator.ACT, lam, T0, float(hparams.EPS), t_first=t_first)
+        self.attr = attr
+        return ops.reattach_phase(ops.online_separate(w, attr, embed, m.separator.ACT), phasor)
+
+    def _empty(self):
+        return torch.empty(self.batch, hparams.MAX_N_SIGNAL, 0, hparams.FEATURE_SIZE, dtype=torch.complex64,
+                           device=self.model.device)
+
+    def _a0(self):
+        '''(A0 [batch, C, E] of the first min(T0, frames held) frames, and the held frames joined)'''
+        embed, w, phasor = (torch.cat(parts, dim=1) for parts in zip(*self.held))
+        T0 = self.model.online[0]
+        a0, _, _ = ops.AnchorAttractorFn.apply(embed[:, :T0].contiguous(), self.anchors, hparams.MAX_N_SIGNAL)
+        return a0, embed, w, phasor
+
+    def _block(self, frames):
+        embed, w, phasor = self._encode(frames)
+        self.embed = embed
+        t_first, self.t = self.t, self.t + frames.shape[1]
+        if self.state is not None:
+            return self._track(embed, w, phasor, t_first)
+        self.held.append((embed, w, phasor))
+        if self.t < self.model.online[0]:
+            return self._empty()
+        a0, embed, w, phasor = self._a0()
+        self.held = []
+        self.state = ops.online_init(a0)
+        return self._track(embed.contiguous(), w.contiguous(), phasor.contiguous(), 0)
+
+    def push(self, frames):
+        '''the next n >= 0 frames of every recording, complex64 [batch, n, F] -> the m frames this call decided,
+        complex64 [batch, C, m, F]'''
+        if frames.dim() != 3 or frames.shape[0] != self.batch or frames.shape[2] != hparams.FEATURE_SIZE \
+                or frames.dtype != torch.complex64:
+            raise ValueError('push takes complex64 [batch = %d, n, F = %d] (got %s %s)'
+                             % (self.batch, hparams.FEATURE_SIZE, frames.dtype, tuple(frames.shape)))
+        with torch.no_grad():
+            parts = [self._block(frames[:, s:s + self.BLOCK]) for s in range(0, frames.shape[1], self.BLOCK)]
+            return torch.cat(parts, dim=2) if parts else self._empty()
+
+    def flush(self):
+        '''end the recording: the frames still held (a recording no longer than the hold: the plain separator with A0
+        of the frames there are, as Model.infer there), else zero frames; then reset()'''
+        with torch.no_grad():
+            out = self._empty()
+            if self.held:
+                a0, embed, w, phasor = self._a0()
+                sep = self.model.separator(w, a0, embed.reshape(self.batch, -1, hparams.EMBED_SIZE))
+                out = ops.reattach_phase(sep, phasor.contiguous())
+        self.reset()
+        return out

@@ -159,10 +159,13 @@ class _RnnEncoderBase(Encoder):
             D = self.NDIR * hdim
         params.append(m.get_variable(self.name + '/output/W', [D, F * E],
                                      _uniform_init(1.85)))  # modules.py:184-191 / :248-255
-        # (NDIR == 1, `lstm-orig`: accepted and ignored, as in the reference's class)
-        with ops.dropout_scope(_dropout_spec(m, s_dropout_keep) if self.NDIR == 2 else None):
-            s_out = ops.RnnEncoderFn.apply(s_signals, hdim, nlayer, self.NDIR, *params)
+        s_out = self._encode(s_signals, hdim, nlayer, params, s_dropout_keep)
         return s_out.reshape(hparams.BATCH_SIZE, -1, F, E)  # modules.py:192-195 / :256-259
+
+    def _encode(self, s_signals, hdim, nlayer, params, s_dropout_keep):
+        # (NDIR == 1, `lstm-orig`: accepted and ignored, as in the reference's class)
+        with ops.dropout_scope(_dropout_spec(self.model, s_dropout_keep) if self.NDIR == 2 else None):
+            return ops.RnnEncoderFn.apply(s_signals, hdim, nlayer, self.NDIR, *params)
 
 
 @hparams.register_encoder('lstm-orig')
@@ -182,6 +185,18 @@ class LstmEncoder(_RnnEncoderBase):
         # only a non-default value overrides it.
         h = hparams.LSTM_HDIM
         return (600 if h == 300 else h), hparams.NUM_LSTM_LAYERS
+
+
+@hparams.register_encoder('lstm-causal')
+class LstmCausalEncoder(LstmEncoder):
+    '''the `lstm-orig` stack with both whole-utterance centrings replaced by the running mean over the frames seen so
+    far (include/danet_causal_hip.h): the embedding of frame t depends on frames <= t only.  NOT in the reference.
+    Same variable names, shapes, initialisers, creation order and `_dims()` as `lstm-orig`, so its parameter files
+    load; it trains on the same recurrent kernels (ops.CausalRnnEncoderFn), and Model.open_stream runs it block by
+    block from carried state.  s_dropout_keep is accepted and ignored, as in `lstm-orig`.'''
+
+    def _encode(self, s_signals, hdim, nlayer, params, s_dropout_keep):
+        return ops.CausalRnnEncoderFn.apply(s_signals, hdim, nlayer, *params)
 
 
 @hparams.register_encoder('bilstm-orig')

@@ -1142,6 +1142,89 @@ def online_attractors(embed, w, a0, act, lam, T0, eps):
     return online_scan(embed.contiguous(), w.contiguous(), online_init(a0), act, lam, T0, eps)
 
 
+# ---- the causal encoder and block-wise streaming (include/danet_causal_hip.h) -----------------------------------
+# On the extension library libdanet_causal_hip.so, mapped at the first call: a run with another encoder and no stream
+# session never gets here.
+CAUSAL_MAX_B = 16                                    # DANET_CAUSAL_MAX_B
+CAUSAL_MAX_TB = 64                                   # DANET_CAUSAL_MAX_TB
+CAUSAL_MAX_H = 608                                   # DANET_CAUSAL_MAX_H
+CAUSAL_MAX_D0 = 1028                                 # DANET_CAUSAL_MAX_D0
+CAUSAL_MAX_L = 8                                     # DANET_CAUSAL_MAX_L
+CAUSAL_MAX_M = 1024                                  # DANET_CAUSAL_MAX_M
+
+
+def causal_center_state(B, dev):
+    '''the state of a fresh utterance: float64 [B, 2] = (S, n), zeros'''
+    return torch.zeros(B, 2, dtype=torch.float64, device=dev)
+
+
+def causal_center_fwd(x, B, T, D, in_layout, ld_in, out, out_layout, ld_out, state):
+    '''danet_causal_center_fwd, ONE launch: out[t] = x[t] - the mean of everything up to and including frame t, from
+    `state` (float64 [B, 2], updated IN PLACE); layouts as for `center`'''
+    assert state.is_cuda and state.dtype == torch.float64 and state.is_contiguous() and tuple(state.shape) == (B, 2), \
+        (state.dtype, state.shape)
+    with _lib.timed('causal_center'):
+        _lib.causal_check(_lib.load_causal().danet_causal_center_fwd(
+            _lib.stream(), B, T, D, ptr(_f32(x)), in_layout, ld_in, ptr(_f32(out)), out_layout, ld_out, ptr(state)))
+    return out
+
+
+def causal_center_bwd(dout, B, T, D, dout_layout, ld_dout, din, din_layout, ld_din):
+    '''danet_causal_center_bwd, ONE launch: the adjoint of causal_center_fwd over a whole utterance from a zero state'''
+    with _lib.timed('causal_center_bwd'):
+        _lib.causal_check(_lib.load_causal().danet_causal_center_bwd(
+            _lib.stream(), B, T, D, ptr(_f32(dout)), dout_layout, ld_dout, ptr(_f32(din)), din_layout, ld_din))
+    return din
+
+
+def causal_lstm_ws_bytes(L, B, Tb, H):
+    '''danet_causal_lstm_ws_bytes: the bytes of the per-layer block buffers'''
+    return _lib.bytes_or_raise(_lib.load_causal().danet_causal_lstm_ws_bytes(int(L), int(B), int(Tb), int(H)),
+                               _lib.causal_check)
+
+
+def causal_lstm_block(x, ldx, D0, Ws, bs, h, c, y=None, ldy=None, ws=None):
+    '''danet_causal_lstm_block: the Tb frames x float32 [Tb, B, ldx] (D0 valid columns) through the L = len(Ws)
+    stacked layers FROM the carried state h, c float32 [L, B, H] (both updated IN PLACE) -> y float32 [Tb, B, ldy], the
+    top layer's output; Tb + L launches'''
+    L = len(Ws)
+    Tb, B = x.shape[0], x.shape[1]
+    H = h.shape[2]
+    dev = x.device
+    assert tuple(h.shape) == (L, B, H) == tuple(c.shape) and h.is_contiguous() and c.is_contiguous(), (h.shape, c.shape)
+    assert x.is_contiguous() and x.shape[2] == ldx, (x.shape, ldx)
+    D = D0
+    for W, b in zip(Ws, bs):
+        assert tuple(W.shape) == (D + H, 4 * H) and W.is_contiguous() and tuple(b.shape) == (4 * H,), (W.shape, b.shape)
+        _f32(W), _f32(b)
+        D = H
+    if y is None:
+        ldy = H
+        y = torch.empty(Tb, B, H, device=dev)
+    nbytes = causal_lstm_ws_bytes(L, B, Tb, H)
+    if ws is None:
+        ws = torch.empty(nbytes // 4, device=dev)
+    wp = (_lib.c_p * L)(*[ptr(W) for W in Ws])
+    bp = (_lib.c_p * L)(*[ptr(b) for b in bs])
+    with _lib.timed('causal_lstm_block'):
+        _lib.causal_check(_lib.load_causal().danet_causal_lstm_block(
+            _lib.stream(), L, B, Tb, D0, H, ptr(_f32(x)), ldx, wp, bp, ptr(_f32(h)), ptr(_f32(c)), ptr(_f32(y)), ldy,
+            ptr(ws), ws.numel() * ws.element_size()))
+    return y
+
+
+def causal_project(A, M, K, N, lda, W, ldw, out=None, ldo=None):
+    '''danet_causal_project, ONE launch: out[M, N] = A[M, K] W[K, N] in the fixed-order arithmetic of the LSTM step;
+    row r of the result does not depend on M'''
+    if out is None:
+        ldo = N
+        out = torch.empty(M, N, device=A.device)
+    with _lib.timed('causal_project'):
+        _lib.causal_check(_lib.load_causal().danet_causal_project(
+            _lib.stream(), M, K, N, ptr(_f32(A)), lda, ptr(_f32(W)), ldw, ptr(_f32(out)), ldo))
+    return out
+
+
 # ---- BSS-eval figures of valid / test (include/danet_bss_hip.h) ----------------------------------------
 # On the extension library libdanet_bss_hip.so, mapped at the first call: a run with EVAL_BSS_SDR null never gets
 # here.  waveforms (ops.metric_synth) -> lagged correlations -> block-Toeplitz systems -> two batched Cholesky
@@ -2997,6 +3080,94 @@ class RnnEncoderFn(torch.autograd.Function):
         join_deferred()
         ctx.ctxs = None
         return (None, None, None, None) + tuple(grads) + (None if direct_out else dWout,)
+
+
+class CausalRnnEncoderFn(torch.autograd.Function):
+    '''Whole `lstm-causal` encoder: RnnEncoderFn with ndir = 1 (the `lstm-orig` stack, on the same recurrent kernels
+    and the same projection) with both whole-utterance centrings replaced by the causal running mean of
+    include/danet_causal_hip.h from a zero state -- the embedding of frame t depends on frames <= t only.
+    x [B,T,F] -> embed [B,T,F*E].  params = (W_0, b_0, W_1, ..., W_out).  No dropout, as `lstm-orig`.'''
+
+    @staticmethod
+    def forward(ctx, x, H, L, *params):
+        x = _f32(x.contiguous())
+        B, T, F = x.shape
+        dev = x.device
+        Wout = params[-1]
+        Fp = (F + 3) // 4 * 4
+        # x - its running mean, switched to time-major, zero-padded to a float4 row
+        xc = torch.empty(T, B, Fp, device=dev)
+        causal_center_fwd(x, B, T, F, 0, F, xc, 1, Fp, causal_center_state(B, dev))
+        ypads = [torch.empty(T + 2, B, H, device=dev) for _ in range(L)]
+        wss = [_lstm_ws(T, B, H, 1, dev)[0] for _ in range(L)]
+        bwss = None
+        if any(ctx.needs_input_grad) and BWD_DB and _L().danet_lstm_bwd_db_supported(T, B, H, 1) == 1:
+            bwss = [_lstm_ws(T, B, H, 1, dev)[0] for _ in range(L)]
+        if bwss is None or not lstm_prefill_train(T, B, H, 1, ypads, wss, bwss):
+            bwss = None
+            lstm_prefill_fwd(T, B, H, ypads, wss)
+        ctx.bwss = bwss
+        ctxs = []
+        cur, ld, D = xc, Fp, F
+        for l in range(L):
+            c = lstm_layer_fwd(cur, ld, D, T, B, H, [params[2 * l]], [params[2 * l + 1]], x_pad_zero=True,
+                               ypad=ypads[l], ws=wss[l])
+            ctxs.append(c)
+            cur, ld, D = c.ypad[1:], H, H
+        # y - its running mean, back to batch-major
+        yc = torch.empty(B, T, D, device=dev)
+        causal_center_fwd(cur, B, T, D, 1, D, yc, 0, D, causal_center_state(B, dev))
+        O = Wout.shape[1]
+        embed = torch.empty(B, T, O, device=dev)
+        big = ((B * T + 127) // 128) * ((O + 127) // 128) >= 1024
+        if _x6_ok(B * T, O, (yc, D, D)):
+            gemm_w(yc, D, Wout, 1, O, embed, B * T, O, D, O, tag='proj')
+        else:
+            gemm(yc, Wout, embed, B * T, O, D, D, O, O, tag='proj',
+                 streamk=(STREAMK & 2) != 0 or (big and STREAMK != 0))
+        ctx.ctxs, ctx.yc, ctx.Wout = ctxs, yc, Wout
+        ctx.dims = (B, T, F, H, L, D, O)
+        return embed
+
+    @staticmethod
+    def backward(ctx, dembed):
+        B, T, F, H, L, D, O = ctx.dims
+        dembed = _f32(dembed.contiguous())
+        dev = dembed.device
+        dWout, direct_out = _grad_target(ctx.Wout, (D, O), dev)
+        dyc = torch.empty(B, T, D, device=dev)
+        x6 = _x6_ok(B * T, D, (dembed, O, O))
+        ev = fork_event(dev) if ((STREAMK & 1) != 0 or x6) else None
+        if x6:                                                # critical path first
+            gemm_w(dembed, O, ctx.Wout, O, 1, dyc, B * T, D, O, D, tag='dYc', stop_event=ev)
+        else:
+            gemm(dembed, ctx.Wout, dyc, B * T, D, O, O, O, D, transB=True, streamk=(STREAMK & 1) != 0,
+                 tag='dYc', stop_event=ev)
+        with _Fork(dev, 2, defer=True, keep=(dembed, ctx.yc), lazy=True, event=ev) as f:
+            if GROUPED_DW:
+                ov = _overlap_dw(H, _x6_tn_ok([(ctx.yc, D, dembed, O, dWout, O, D, O, 0.0)], B * T))
+                f.run(1 if ov else 0, lambda: gemm_group(
+                    [(ctx.yc, D, dembed, O, dWout, O, D, O, 1.0 if direct_out else 0.0)], B * T,
+                    transA=True, max_workgroups=GROUPED_DW_WGS if ov else 512))
+            else:
+                f.run(1, lambda: gemm(ctx.yc, dembed, dWout, D, O, B * T, D, O, O, transA=True,
+                                      beta=1.0 if direct_out else 0.0,
+                                      max_workgroups=2 * OVERLAP_GEMM_WGS, tag='dWout'))
+            if GRAD_READY_HOOKS and _fast() and direct_out:
+                f.after_all(lambda: _fire_grad_ready(('out',), [ctx.Wout]))
+        dy = torch.empty(T, B, D, device=dev)
+        causal_center_bwd(dyc, B, T, D, 0, D, dy, 1, D)      # the running mean is not self-adjoint
+        grads = [None] * (2 * L)
+        bwss = ctx.bwss if ctx.bwss is not None else [None] * L
+        ctx.bwss = None
+        for l in reversed(range(L)):
+            dx, dWs, dbs = lstm_layer_bwd(ctx.ctxs[l], dy, need_dx=(l > 0), layer_tag=l,
+                                          is_top=(l == L - 1), ws_prefilled=bwss[l])
+            grads[2 * l], grads[2 * l + 1] = dWs[0], dbs[0]
+            dy = dx
+        join_deferred()
+        ctx.ctxs = None
+        return (None, None, None) + tuple(grads) + (None if direct_out else dWout,)
 
 
 # ---------------------------------------------------------------------------
