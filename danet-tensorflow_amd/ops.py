@@ -33,6 +33,11 @@ def _ws(nbytes, dev):
     return w, w.numel()
 
 
+def _ptrs(ts):
+    '''the C array of the tensors' device pointers'''
+    return (_lib.c_p * len(ts))(*[ptr(t) for t in ts])
+
+
 # ---------------------------------------------------------------------------
 # raw wrappers (no autograd)
 # ---------------------------------------------------------------------------
@@ -1204,12 +1209,10 @@ def causal_lstm_block(x, ldx, D0, Ws, bs, h, c, y=None, ldy=None, ws=None):
     nbytes = causal_lstm_ws_bytes(L, B, Tb, H)
     if ws is None:
         ws = torch.empty(nbytes // 4, device=dev)
-    wp = (_lib.c_p * L)(*[ptr(W) for W in Ws])
-    bp = (_lib.c_p * L)(*[ptr(b) for b in bs])
     with _lib.timed('causal_lstm_block'):
         _lib.causal_check(_lib.load_causal().danet_causal_lstm_block(
-            _lib.stream(), L, B, Tb, D0, H, ptr(_f32(x)), ldx, wp, bp, ptr(_f32(h)), ptr(_f32(c)), ptr(_f32(y)), ldy,
-            ptr(ws), ws.numel() * ws.element_size()))
+            _lib.stream(), L, B, Tb, D0, H, ptr(_f32(x)), ldx, _ptrs(Ws), _ptrs(bs), ptr(_f32(h)), ptr(_f32(c)),
+            ptr(_f32(y)), ldy, ptr(ws), ws.numel() * ws.element_size()))
     return y
 
 
@@ -2614,10 +2617,7 @@ def join_deferred():
 
 def lstm_prefill_fwd(T, B, ldy, ypads, wss):
     '''ONE fill launch for the output buffers (+ workspaces) of several forward launches'''
-    n = len(ypads)
-    yp = (_lib.c_p * n)(*[ptr(y) for y in ypads])
-    wp = (_lib.c_p * n)(*[ptr(w) for w in wss])
-    check(_L().danet_lstm_fwd_prefill(_lib.stream(), T, B, ldy, n, yp, wp))
+    check(_L().danet_lstm_fwd_prefill(_lib.stream(), T, B, ldy, len(ypads), _ptrs(ypads), _ptrs(wss)))
 
 
 # the input's centring and the recurrent launches' prefill in one launch (danet_encoder_prologue)
@@ -2627,12 +2627,10 @@ ENC_PROLOGUE = _lib.expert('enc_prologue', True)
 def encoder_prologue(x, B, T, F, xc, Fp, H, ndir, ypads, fwd_wss, bwd_wss):
     '''xc[T, B, Fp] = x[B, T, F] - mean_{t,f}(x) (time-major, zero pad) AND the prefill of the n recurrent
     launches' buffers (bwd_wss: + the BPTT rings), one launch; False: the rings were NOT prefilled'''
-    n = len(ypads)
-    yp = (_lib.c_p * n)(*[ptr(y) for y in ypads])
-    fp = (_lib.c_p * n)(*[ptr(w) for w in fwd_wss])
-    bp = (_lib.c_p * n)(*[ptr(w) for w in bwd_wss]) if bwd_wss is not None else None
+    bp = _ptrs(bwd_wss) if bwd_wss is not None else None
     scratch = torch.empty(_lib.ws_bytes(_lib.WS_CENTER_MEAN, B) // 4, dtype=torch.float32, device=x.device)
-    args = (_lib.stream(), B, T, F, ptr(_f32(x)), 0, F, ptr(xc), 1, Fp, ptr(scratch), H, ndir, ndir * H, n, yp, fp)
+    args = (_lib.stream(), B, T, F, ptr(_f32(x)), 0, F, ptr(xc), 1, Fp, ptr(scratch), H, ndir, ndir * H, len(ypads),
+            _ptrs(ypads), _ptrs(fwd_wss))
     rc = _L().danet_encoder_prologue(*args, bp)
     if rc == -3 and bp is not None:      # BPTT geometry outside the reduce-scatter kernel: it prefills itself
         check(_L().danet_encoder_prologue(*args, None))
@@ -2645,11 +2643,28 @@ def lstm_prefill_train(T, B, H, ndir, ypads, fwd_wss, bwd_wss):
     '''ONE fill launch for the forward launches' buffers AND the partial-dh rings of the BPTT launches
     that will follow; False (nothing launched) when the shape takes the all-gather BPTT kernel, which
     prefills its own exchange medium'''
-    n = len(ypads)
-    yp = (_lib.c_p * n)(*[ptr(y) for y in ypads])
-    fp = (_lib.c_p * n)(*[ptr(w) for w in fwd_wss])
-    bp = (_lib.c_p * n)(*[ptr(w) for w in bwd_wss])
-    return _L().danet_lstm_train_prefill(_lib.stream(), T, B, H, ndir, ndir * H, n, yp, fp, bp) == 0
+    return _L().danet_lstm_train_prefill(_lib.stream(), T, B, H, ndir, ndir * H, len(ypads), _ptrs(ypads),
+                                         _ptrs(fwd_wss), _ptrs(bwd_wss)) == 0
+
+
+def _stack_buffers(train, n, T, B, H, ndir, dev):
+    '''(ypads, wss, bwss) of n recurrent launches: their output buffers and workspaces, and on a train step whose
+    shape the reduce-scatter BPTT kernel covers the workspaces of the BPTT launches (their rings), else None'''
+    ypads = [torch.empty(T + 2, B, ndir * H, device=dev) for _ in range(n)]
+    wss = [_lstm_ws(T, B, H, ndir, dev)[0] for _ in range(n)]
+    bwss = None
+    if train and BWD_DB and _L().danet_lstm_bwd_db_supported(T, B, H, ndir) == 1:
+        bwss = [_lstm_ws(T, B, H, ndir, dev)[0] for _ in range(n)]
+    return ypads, wss, bwss
+
+
+def _stack_prefill(T, B, H, ndir, ypads, wss, bwss):
+    '''ONE fill launch for the buffers of `_stack_buffers`: the train prefill, or the forward prefill where there
+    are no rings or the train prefill declines the shape; returns bwss, None if the rings were NOT prefilled'''
+    if bwss is None or not lstm_prefill_train(T, B, H, ndir, ypads, wss, bwss):
+        bwss = None
+        lstm_prefill_fwd(T, B, ndir * H, ypads, wss)
+    return bwss
 
 
 def lstm_layer_fwd(x, ldx, D, T, B, H, Ws, bs, x_pad_zero=False, ypad=None, ws=None):
@@ -2780,14 +2795,17 @@ def lstm_layer_bwd(c, dy, need_dx, layer_tag=None, is_top=False, ws_prefilled=No
     # dX -> next BPTT) when a side chain is forked behind this launch anyway
     # (not for the bottom layer: its weight-gradient group takes every CU on the main stream
     # and the side chain's reduce would sit behind it for the group's whole duration)
+    def hprev_of(d):
+        # Hprev(t) = ypad block t (fwd) / block t+2 (bwd)
+        return c.ypad.view(-1)[(0 if d == 0 else 2 * B * ldy + H):]
+
     def group_problems():
-        # dWx = X^T da and dWh = Hprev^T da of every direction (Hprev(t) = ypad block t (fwd) / t+2 (bwd))
+        # dWx = X^T da and dWh = Hprev^T da of every direction
         probs = []
         for d in range(ndir):
             bW = 1.0 if direct[d][0] else 0.0
-            hprev = c.ypad.view(-1)[(0 if d == 0 else 2 * B * ldy + H):]
             probs.append((c.x, c.ldx, das[d], 4 * H, dWs[d], 4 * H, D, 4 * H, bW))
-            probs.append((hprev, ldy, das[d], 4 * H, dWs[d][D:], 4 * H, H, 4 * H, bW))
+            probs.append((hprev_of(d), ldy, das[d], 4 * H, dWs[d][D:], 4 * H, H, 4 * H, bW))
         return probs
     overlap = _overlap_dw(H, _x6_tn_ok(group_problems(), T * B))
     db_deferred = (db_in_kernel and DB_DEFER and GROUPED_DW and SIDE_STREAMS > 0 and
@@ -2811,16 +2829,11 @@ def lstm_layer_bwd(c, dy, need_dx, layer_tag=None, is_top=False, ws_prefilled=No
         # dWx = X^T da
         gemm(c.x, das[d], dWs[d], D, 4 * H, T * B, c.ldx, 4 * H, 4 * H, transA=True, beta=bW,
              max_workgroups=cap)
-        # dWh = Hprev^T da; Hprev(t) = ypad block t (fwd) / block t+2 (bwd)
-        hprev = c.ypad.view(-1)[(0 if d == 0 else 2 * B * ldy + H):]
-        gemm(hprev, das[d], dWs[d][D:], H, 4 * H, T * B, ldy, 4 * H, 4 * H, transA=True, beta=bW,
+        # dWh = Hprev^T da
+        gemm(hprev_of(d), das[d], dWs[d][D:], H, 4 * H, T * B, ldy, 4 * H, 4 * H, transA=True, beta=bW,
              max_workgroups=cap)
         if not db_in_kernel:
             colsum(das[d], T * B, 4 * H, 4 * H, dbs[d], beta=bb)
-
-    def hprev_of(d):
-        # Hprev(t) = ypad block t (fwd) / block t+2 (bwd)
-        return c.ypad.view(-1)[(0 if d == 0 else 2 * B * ldy + H):]
 
     def weight_grads_grouped(wgs=GROUPED_DW_WGS, with_bias=True):
         # dWx = X^T da and dWh = Hprev^T da of every direction: one launch
@@ -2963,6 +2976,128 @@ class LstmLayerFn(torch.autograd.Function):
         return tuple(out)
 
 
+def _project_fwd(rows, K, W, B, T, streamk):
+    '''the encoders' bias-free projection embed [B, T, O] = rows [B*T, K] W [K, O]; streamk: the schedule of the
+    product where it does not run on the packed weight'''
+    O = W.shape[1]
+    embed = torch.empty(B, T, O, device=rows.device)
+    if _x6_ok(B * T, O, (rows, K, K)):
+        gemm_w(rows, K, W, 1, O, embed, B * T, O, K, O, tag='proj')
+    else:
+        gemm(rows, W, embed, B * T, O, K, K, O, O, tag='proj', streamk=streamk)
+    return embed
+
+
+def _encoder_center(causal, x, B, T, D, in_layout, ld_in, out, out_layout, ld_out):
+    '''an encoder's centring: x minus its whole-utterance mean, or (causal) minus its running mean from a zero state'''
+    if causal:
+        return causal_center_fwd(x, B, T, D, in_layout, ld_in, out, out_layout, ld_out,
+                                 causal_center_state(B, x.device))
+    return center(x, B, T, D, in_layout, ld_in, out, out_layout, ld_out)
+
+
+def _rnn_encoder_fwd(ctx, causal, x, H, L, ndir, params):
+    '''centre -> L stacked (bi)LSTM layers -> centre -> bias-free projection: the forward of RnnEncoderFn and
+    (causal) of CausalRnnEncoderFn, which differ in the centrings only'''
+    x = _f32(x.contiguous())
+    B, T, F = x.shape
+    dev = x.device
+    Wout = params[-1]
+    Fp = (F + 3) // 4 * 4
+    # x - its mean, switched to time-major, zero-padded to a float4 row                modules.py:209-210
+    xc = torch.empty(T, B, Fp, device=dev)
+    ctxs = []
+    cur, ld, D = xc, Fp, F
+    # output buffers + workspaces of ALL layers (a train step: + the BPTT launches' rings), prefilled
+    # by ONE fill -- which rides in the whole-utterance centring launch (danet_encoder_prologue)
+    ypads, wss, bwss = _stack_buffers(any(ctx.needs_input_grad), L, T, B, H, ndir, dev)
+    if causal or not ENC_PROLOGUE:
+        _encoder_center(causal, x, B, T, F, 0, F, xc, 1, Fp)
+        bwss = _stack_prefill(T, B, H, ndir, ypads, wss, bwss)
+    elif not encoder_prologue(x, B, T, F, xc, Fp, H, ndir, ypads, wss, bwss):
+        bwss = None
+    ctx.bwss = bwss
+    spec = _dropout_cur[0] if ndir == 2 else None
+    ctx.drop = (spec, spec.take(L)) if spec is not None else None
+    for l in range(L):                                    # modules.py:223-242
+        Ws = [params[(l * ndir + d) * 2] for d in range(ndir)]
+        bs = [params[(l * ndir + d) * 2 + 1] for d in range(ndir)]
+        # (the centre kernel zero-fills the float4 pad of layer 0's rows; deeper layers
+        # read ypad, whose row length is a multiple of 4)
+        c = lstm_layer_fwd(cur, ld, D, T, B, H, Ws, bs, x_pad_zero=True, ypad=ypads[l],
+                           ws=wss[l])
+        ctxs.append(c)
+        cur, ld, D = c.ypad[1:], ndir * H, ndir * H
+        if spec is not None:                              # modules.py:137
+            cur = dropout_apply(cur, torch.empty(T, B, D, device=dev), T * B, D, D, D, spec,
+                                ctx.drop[1] + l)
+    # y - its mean, back to batch-major                     modules.py:244-245
+    yc = torch.empty(B, T, D, device=dev)
+    _encoder_center(causal, cur, B, T, D, 1, D, yc, 0, D)
+    O = Wout.shape[1]
+    # (hybrid stream-K pays for the projection only with >= 4 tiles per CU: cfg 4, 1312 tiles,
+    # 248 -> 238 us; cfg 2, 672 tiles, 126 -> 132 us)
+    big = ((B * T + 127) // 128) * ((O + 127) // 128) >= 1024
+    embed = _project_fwd(yc, D, Wout, B, T, (STREAMK & 2) != 0 or (big and STREAMK != 0))     # modules.py:249-255
+    ctx.ctxs, ctx.yc, ctx.Wout = ctxs, yc, Wout
+    ctx.dims = (B, T, F, H, L, ndir, D, O)
+    ctx.causal = causal
+    return embed
+
+
+def _rnn_encoder_bwd(ctx, dembed):
+    '''the backward of `_rnn_encoder_fwd`: the gradients of its params, in their order (None: accumulated
+    straight into .grad)'''
+    B, T, F, H, L, ndir, D, O = ctx.dims
+    dembed = _f32(dembed.contiguous())
+    dev = dembed.device
+    dWout, direct_out = _grad_target(ctx.Wout, (D, O), dev)
+    dyc = torch.empty(B, T, D, device=dev)
+    x6 = _x6_ok(B * T, D, (dembed, O, O))
+    ev = fork_event(dev) if ((STREAMK & 1) != 0 or x6) else None
+    if x6:                                                # critical path first
+        gemm_w(dembed, O, ctx.Wout, O, 1, dyc, B * T, D, O, D, tag='dYc', stop_event=ev)
+    else:
+        gemm(dembed, ctx.Wout, dyc, B * T, D, O, O, O, D, transB=True, streamk=(STREAMK & 1) != 0,
+             tag='dYc', stop_event=ev)
+    with _Fork(dev, 2, defer=True, keep=(dembed, ctx.yc), lazy=True, event=ev) as f:
+        if GROUPED_DW:    # alone on its stream under the top layer's BPTT kernel (or serial)
+            ov = _overlap_dw(H, _x6_tn_ok([(ctx.yc, D, dembed, O, dWout, O, D, O, 0.0)], B * T))
+            f.run(1 if ov else 0, lambda: gemm_group(
+                [(ctx.yc, D, dembed, O, dWout, O, D, O, 1.0 if direct_out else 0.0)], B * T,
+                transA=True, max_workgroups=GROUPED_DW_WGS if ov else 512))
+        else:
+            f.run(1, lambda: gemm(ctx.yc, dembed, dWout, D, O, B * T, D, O, O, transA=True,
+                                  beta=1.0 if direct_out else 0.0,
+                                  max_workgroups=2 * OVERLAP_GEMM_WGS, tag='dWout'))
+        if GRAD_READY_HOOKS and _fast() and direct_out:
+            f.after_all(lambda: _fire_grad_ready(('out',), [ctx.Wout]))
+    dy = torch.empty(T, B, D, device=dev)
+    if ctx.causal:
+        causal_center_bwd(dyc, B, T, D, 0, D, dy, 1, D)      # the running mean is not self-adjoint
+    else:
+        center(dyc, B, T, D, 0, D, dy, 1, D)                 # centre is self-adjoint
+    drop = ctx.drop
+    if drop is not None:                                 # the top layer's mask (dy is ours: in place)
+        dropout_apply(dy, dy, T * B, D, D, D, drop[0], drop[1] + L - 1)
+    grads = [None] * (2 * L * ndir)
+    # partial-dh rings of all layers' BPTT launches: prefilled by the forward pass's fill launch
+    bwss = ctx.bwss if ctx.bwss is not None else [None] * L
+    ctx.bwss = None
+    for l in reversed(range(L)):
+        dx, dWs, dbs = lstm_layer_bwd(ctx.ctxs[l], dy, need_dx=(l > 0), layer_tag=l,
+                                      is_top=(l == L - 1), ws_prefilled=bwss[l],
+                                      dx_drop=(drop[0], drop[1] + l - 1) if (drop is not None and l > 0)
+                                      else None)
+        for d in range(ndir):
+            grads[(l * ndir + d) * 2] = dWs[d]
+            grads[(l * ndir + d) * 2 + 1] = dbs[d]
+        dy = dx
+    join_deferred()
+    ctx.ctxs = None
+    return tuple(grads) + (None if direct_out else dWout,)
+
+
 class RnnEncoderFn(torch.autograd.Function):
     '''Whole `bilstm-orig` / `lstm-orig` encoder (app/modules.py:148-260):
     mean-centre -> L stacked (bi)LSTM layers -> mean-centre -> bias-free output
@@ -2977,109 +3112,11 @@ class RnnEncoderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, H, L, ndir, *params):
-        x = _f32(x.contiguous())
-        B, T, F = x.shape
-        dev = x.device
-        Wout = params[-1]
-        Fp = (F + 3) // 4 * 4
-        # x - mean_{t,f}(x), switched to time-major, zero-padded to a float4 row       modules.py:209-210
-        xc = torch.empty(T, B, Fp, device=dev)
-        ctxs = []
-        cur, ld, D = xc, Fp, F
-        # output buffers + workspaces of ALL layers (a train step: + the BPTT launches' rings), prefilled
-        # by ONE fill -- which rides in the centring launch (danet_encoder_prologue)
-        ypads = [torch.empty(T + 2, B, ndir * H, device=dev) for _ in range(L)]
-        wss = [_lstm_ws(T, B, H, ndir, dev)[0] for _ in range(L)]
-        bwss = None
-        if any(ctx.needs_input_grad) and BWD_DB and _L().danet_lstm_bwd_db_supported(T, B, H, ndir) == 1:
-            bwss = [_lstm_ws(T, B, H, ndir, dev)[0] for _ in range(L)]
-        if not ENC_PROLOGUE:
-            center(x, B, T, F, 0, F, xc, 1, Fp)
-            if bwss is None or not lstm_prefill_train(T, B, H, ndir, ypads, wss, bwss):
-                bwss = None
-                lstm_prefill_fwd(T, B, ndir * H, ypads, wss)
-        else:
-            if not encoder_prologue(x, B, T, F, xc, Fp, H, ndir, ypads, wss, bwss):
-                bwss = None
-        ctx.bwss = bwss
-        spec = _dropout_cur[0] if ndir == 2 else None
-        ctx.drop = (spec, spec.take(L)) if spec is not None else None
-        for l in range(L):                                    # modules.py:223-242
-            Ws = [params[(l * ndir + d) * 2] for d in range(ndir)]
-            bs = [params[(l * ndir + d) * 2 + 1] for d in range(ndir)]
-            # (the centre kernel zero-fills the float4 pad of layer 0's rows; deeper layers
-            # read ypad, whose row length is a multiple of 4)
-            c = lstm_layer_fwd(cur, ld, D, T, B, H, Ws, bs, x_pad_zero=True, ypad=ypads[l],
-                               ws=wss[l])
-            ctxs.append(c)
-            cur, ld, D = c.ypad[1:], ndir * H, ndir * H
-            if spec is not None:                              # modules.py:137
-                cur = dropout_apply(cur, torch.empty(T, B, D, device=dev), T * B, D, D, D, spec,
-                                    ctx.drop[1] + l)
-        # y - mean_{t,h}(y), back to batch-major                modules.py:244-245
-        yc = torch.empty(B, T, D, device=dev)
-        center(cur, B, T, D, 1, D, yc, 0, D)
-        O = Wout.shape[1]
-        embed = torch.empty(B, T, O, device=dev)
-        # (hybrid stream-K pays for the projection only with >= 4 tiles per CU: cfg 4, 1312 tiles,
-        # 248 -> 238 us; cfg 2, 672 tiles, 126 -> 132 us)
-        big = ((B * T + 127) // 128) * ((O + 127) // 128) >= 1024
-        if _x6_ok(B * T, O, (yc, D, D)):
-            gemm_w(yc, D, Wout, 1, O, embed, B * T, O, D, O, tag='proj')     # modules.py:249-255
-        else:
-            gemm(yc, Wout, embed, B * T, O, D, D, O, O, tag='proj',
-                 streamk=(STREAMK & 2) != 0 or (big and STREAMK != 0))
-        ctx.ctxs, ctx.yc, ctx.Wout = ctxs, yc, Wout
-        ctx.dims = (B, T, F, H, L, ndir, D, O)
-        return embed
+        return _rnn_encoder_fwd(ctx, False, x, H, L, ndir, params)
 
     @staticmethod
     def backward(ctx, dembed):
-        B, T, F, H, L, ndir, D, O = ctx.dims
-        dembed = _f32(dembed.contiguous())
-        dev = dembed.device
-        dWout, direct_out = _grad_target(ctx.Wout, (D, O), dev)
-        dyc = torch.empty(B, T, D, device=dev)
-        x6 = _x6_ok(B * T, D, (dembed, O, O))
-        ev = fork_event(dev) if ((STREAMK & 1) != 0 or x6) else None
-        if x6:                                                # critical path first
-            gemm_w(dembed, O, ctx.Wout, O, 1, dyc, B * T, D, O, D, tag='dYc', stop_event=ev)
-        else:
-            gemm(dembed, ctx.Wout, dyc, B * T, D, O, O, O, D, transB=True, streamk=(STREAMK & 1) != 0,
-                 tag='dYc', stop_event=ev)
-        with _Fork(dev, 2, defer=True, keep=(dembed, ctx.yc), lazy=True, event=ev) as f:
-            if GROUPED_DW:    # alone on its stream under the top layer's BPTT kernel (or serial)
-                ov = _overlap_dw(H, _x6_tn_ok([(ctx.yc, D, dembed, O, dWout, O, D, O, 0.0)], B * T))
-                f.run(1 if ov else 0, lambda: gemm_group(
-                    [(ctx.yc, D, dembed, O, dWout, O, D, O, 1.0 if direct_out else 0.0)], B * T,
-                    transA=True, max_workgroups=GROUPED_DW_WGS if ov else 512))
-            else:
-                f.run(1, lambda: gemm(ctx.yc, dembed, dWout, D, O, B * T, D, O, O, transA=True,
-                                      beta=1.0 if direct_out else 0.0,
-                                      max_workgroups=2 * OVERLAP_GEMM_WGS, tag='dWout'))
-            if GRAD_READY_HOOKS and _fast() and direct_out:
-                f.after_all(lambda: _fire_grad_ready(('out',), [ctx.Wout]))
-        dy = torch.empty(T, B, D, device=dev)
-        center(dyc, B, T, D, 0, D, dy, 1, D)                 # centre is self-adjoint
-        drop = ctx.drop
-        if drop is not None:                                 # the top layer's mask (dy is ours: in place)
-            dropout_apply(dy, dy, T * B, D, D, D, drop[0], drop[1] + L - 1)
-        grads = [None] * (2 * L * ndir)
-        # partial-dh rings of all layers' BPTT launches: prefilled by the forward pass's fill launch
-        bwss = ctx.bwss if ctx.bwss is not None else [None] * L
-        ctx.bwss = None
-        for l in reversed(range(L)):
-            dx, dWs, dbs = lstm_layer_bwd(ctx.ctxs[l], dy, need_dx=(l > 0), layer_tag=l,
-                                          is_top=(l == L - 1), ws_prefilled=bwss[l],
-                                          dx_drop=(drop[0], drop[1] + l - 1) if (drop is not None and l > 0)
-                                          else None)
-            for d in range(ndir):
-                grads[(l * ndir + d) * 2] = dWs[d]
-                grads[(l * ndir + d) * 2 + 1] = dbs[d]
-            dy = dx
-        join_deferred()
-        ctx.ctxs = None
-        return (None, None, None, None) + tuple(grads) + (None if direct_out else dWout,)
+        return (None, None, None, None) + _rnn_encoder_bwd(ctx, dembed)
 
 
 class CausalRnnEncoderFn(torch.autograd.Function):
@@ -3090,84 +3127,11 @@ class CausalRnnEncoderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, H, L, *params):
-        x = _f32(x.contiguous())
-        B, T, F = x.shape
-        dev = x.device
-        Wout = params[-1]
-        Fp = (F + 3) // 4 * 4
-        # x - its running mean, switched to time-major, zero-padded to a float4 row
-        xc = torch.empty(T, B, Fp, device=dev)
-        causal_center_fwd(x, B, T, F, 0, F, xc, 1, Fp, causal_center_state(B, dev))
-        ypads = [torch.empty(T + 2, B, H, device=dev) for _ in range(L)]
-        wss = [_lstm_ws(T, B, H, 1, dev)[0] for _ in range(L)]
-        bwss = None
-        if any(ctx.needs_input_grad) and BWD_DB and _L().danet_lstm_bwd_db_supported(T, B, H, 1) == 1:
-            bwss = [_lstm_ws(T, B, H, 1, dev)[0] for _ in range(L)]
-        if bwss is None or not lstm_prefill_train(T, B, H, 1, ypads, wss, bwss):
-            bwss = None
-            lstm_prefill_fwd(T, B, H, ypads, wss)
-        ctx.bwss = bwss
-        ctxs = []
-        cur, ld, D = xc, Fp, F
-        for l in range(L):
-            c = lstm_layer_fwd(cur, ld, D, T, B, H, [params[2 * l]], [params[2 * l + 1]], x_pad_zero=True,
-                               ypad=ypads[l], ws=wss[l])
-            ctxs.append(c)
-            cur, ld, D = c.ypad[1:], H, H
-        # y - its running mean, back to batch-major
-        yc = torch.empty(B, T, D, device=dev)
-        causal_center_fwd(cur, B, T, D, 1, D, yc, 0, D, causal_center_state(B, dev))
-        O = Wout.shape[1]
-        embed = torch.empty(B, T, O, device=dev)
-        big = ((B * T + 127) // 128) * ((O + 127) // 128) >= 1024
-        if _x6_ok(B * T, O, (yc, D, D)):
-            gemm_w(yc, D, Wout, 1, O, embed, B * T, O, D, O, tag='proj')
-        else:
-            gemm(yc, Wout, embed, B * T, O, D, D, O, O, tag='proj',
-                 streamk=(STREAMK & 2) != 0 or (big and STREAMK != 0))
-        ctx.ctxs, ctx.yc, ctx.Wout = ctxs, yc, Wout
-        ctx.dims = (B, T, F, H, L, D, O)
-        return embed
+        return _rnn_encoder_fwd(ctx, True, x, H, L, 1, params)
 
     @staticmethod
     def backward(ctx, dembed):
-        B, T, F, H, L, D, O = ctx.dims
-        dembed = _f32(dembed.contiguous())
-        dev = dembed.device
-        dWout, direct_out = _grad_target(ctx.Wout, (D, O), dev)
-        dyc = torch.empty(B, T, D, device=dev)
-        x6 = _x6_ok(B * T, D, (dembed, O, O))
-        ev = fork_event(dev) if ((STREAMK & 1) != 0 or x6) else None
-        if x6:                                                # critical path first
-            gemm_w(dembed, O, ctx.Wout, O, 1, dyc, B * T, D, O, D, tag='dYc', stop_event=ev)
-        else:
-            gemm(dembed, ctx.Wout, dyc, B * T, D, O, O, O, D, transB=True, streamk=(STREAMK & 1) != 0,
-                 tag='dYc', stop_event=ev)
-        with _Fork(dev, 2, defer=True, keep=(dembed, ctx.yc), lazy=True, event=ev) as f:
-            if GROUPED_DW:
-                ov = _overlap_dw(H, _x6_tn_ok([(ctx.yc, D, dembed, O, dWout, O, D, O, 0.0)], B * T))
-                f.run(1 if ov else 0, lambda: gemm_group(
-                    [(ctx.yc, D, dembed, O, dWout, O, D, O, 1.0 if direct_out else 0.0)], B * T,
-                    transA=True, max_workgroups=GROUPED_DW_WGS if ov else 512))
-            else:
-                f.run(1, lambda: gemm(ctx.yc, dembed, dWout, D, O, B * T, D, O, O, transA=True,
-                                      beta=1.0 if direct_out else 0.0,
-                                      max_workgroups=2 * OVERLAP_GEMM_WGS, tag='dWout'))
-            if GRAD_READY_HOOKS and _fast() and direct_out:
-                f.after_all(lambda: _fire_grad_ready(('out',), [ctx.Wout]))
-        dy = torch.empty(T, B, D, device=dev)
-        causal_center_bwd(dyc, B, T, D, 0, D, dy, 1, D)      # the running mean is not self-adjoint
-        grads = [None] * (2 * L)
-        bwss = ctx.bwss if ctx.bwss is not None else [None] * L
-        ctx.bwss = None
-        for l in reversed(range(L)):
-            dx, dWs, dbs = lstm_layer_bwd(ctx.ctxs[l], dy, need_dx=(l > 0), layer_tag=l,
-                                          is_top=(l == L - 1), ws_prefilled=bwss[l])
-            grads[2 * l], grads[2 * l + 1] = dWs[0], dbs[0]
-            dy = dx
-        join_deferred()
-        ctx.ctxs = None
-        return (None, None, None) + tuple(grads) + (None if direct_out else dWout,)
+        return (None, None, None) + _rnn_encoder_bwd(ctx, dembed)
 
 
 # ---------------------------------------------------------------------------
@@ -3281,14 +3245,8 @@ class ConvBiLstmEncoderFn(torch.autograd.Function):
         Wd = params[24]
         O = Wd.shape[1]
         # output buffers + workspaces of both recurrent launches (a train step: + the BPTT rings), ONE fill
-        ypads = [torch.empty(T4 + 2, B, D, device=dev) for _ in range(2)]
-        wss = [_lstm_ws(T4, B, H, 2, dev)[0] for _ in range(2)]
-        bwss = None
-        if any(ctx.needs_input_grad) and BWD_DB and _L().danet_lstm_bwd_db_supported(T4, B, H, 2) == 1:
-            bwss = [_lstm_ws(T4, B, H, 2, dev)[0] for _ in range(2)]
-        if bwss is None or not lstm_prefill_train(T4, B, H, 2, ypads, wss, bwss):
-            bwss = None
-            lstm_prefill_fwd(T4, B, D, ypads, wss)
+        ypads, wss, bwss = _stack_buffers(any(ctx.needs_input_grad), 2, T4, B, H, 2, dev)
+        bwss = _stack_prefill(T4, B, H, 2, ypads, wss, bwss)
         u8 = torch.uint8
         a0 = conv_fwd(ds[0], x, *cw[0], torch.empty(B, 8, T, F, device=dev))            # modules.py:290-293
         am1 = torch.empty(B, 16, T2, N4, dtype=u8, device=dev)
@@ -3317,11 +3275,7 @@ class ConvBiLstmEncoderFn(torch.autograd.Function):
         mid4 = conv_fwd(ds[5], a4, *cw[5], torch.empty(B, 16, T2, N4, device=dev))       # :344-353
         a6 = conv_fwd(ds[6], mid4, *cw[6], torch.empty(B, 16, T2, N4, device=dev))       # :355-358
         rows = conv_fwd(ds[7], a6, *cw[7], torch.empty(B * T, nfft, device=dev))         # :359-366
-        embed = torch.empty(B, T, O, device=dev)
-        if _x6_ok(B * T, O, (rows, nfft, nfft)):                                         # :369-371
-            gemm_w(rows, nfft, Wd, 1, O, embed, B * T, O, nfft, O, tag='proj')
-        else:
-            gemm(rows, Wd, embed, B * T, O, nfft, nfft, O, O, tag='proj')
+        embed = _project_fwd(rows, nfft, Wd, B, T, False)                                # :369-371
         if debug is not None:
             debug.update(conv_act=conv_act, lstm_act=lstm_act, mid4=mid4)
         ctx.bwss = bwss

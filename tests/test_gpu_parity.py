@@ -344,6 +344,71 @@ def test_encoder_prologue_equals_center_plus_prefill(B, train):
     assert int(yp2[0].view(torch.int32)[1, 0, 0]) == -1 and float(yp2[0][0].abs().max()) == 0.0
 
 
+@pytest.mark.parametrize('B,T,H,ndir,rings', [(32, 8, 300, 2, True), (3, 10, 8, 2, False), (3, 10, 8, 1, False)])
+def test_encoder_step_without_the_prologue_is_bit_equal(B, T, H, ndir, rings, monkeypatch):
+    '''RnnEncoderFn forward + backward end to end with ops.ENC_PROLOGUE off (centre, then the prefill launch: the
+    sequence the causal encoder always takes) against the same step with the switch as it is: the embedding and
+    every parameter gradient bit for bit.  The control -- the unchanged setting twice -- tells a switch that
+    changes bits from a step that is not reproducible.  Then the switched-off run against float64 autograd.
+    F = 9: Fp = 12, the float4 pad of the centred rows is there.
+    rings: the benchmark's BPTT geometry (it depends on B and H alone) -- the library reports support and the
+    forward fill prefills the BPTT rings (lstm_prefill_train, or the prologue's rider).
+    not rings: a train step that allocates no rings, so the fill is lstm_prefill_fwd (or the prologue with the
+    forward lists).  No shape the recurrent kernels run gets there by itself: the library reports no support for
+    H % 4 != 0 (asserted for H = 6), but every recurrent launch refuses such a width too
+    (test_lstm_unsupported_shapes_fail_loudly), and danet_lstm_bwd has no kernel outside the reduce-scatter
+    geometry.  So these cases run at H = 8 with ops.BWD_DB off, which is the one way a train step takes that
+    branch: bias gradients by column sums, the BPTT launches fill their own rings.'''
+    from danet_amd import ops, _lib
+    from gpu_helpers import GTOL, oracle_threads
+    nfft, L, E = 16, 2, 3
+    F = nfft // 2 + 1
+    lib = _lib.load()
+    if rings:
+        assert lib.danet_lstm_bwd_db_supported(T, B, H, ndir) == 1
+    else:
+        assert lib.danet_lstm_bwd_db_supported(T, B, 6, ndir) == 0
+        monkeypatch.setattr(ops, 'BWD_DB', False)
+    rng = np.random.RandomState(B + ndir)
+    x = np.abs(rng.randn(B, T, F)).astype(np.float32)
+    r = 0.75 / np.sqrt(H)
+    names, P, Din = [], [], F
+    for l in range(L):
+        for dn in (('_fwd', '_bwd') if ndir == 2 else ('',)):
+            names += ['global/encoder/lstm%d%s/LSTM/linear/%s' % (l, dn, v) for v in ('W', 'B')]
+            P.append(rng.uniform(-r, r, (Din + H, 4 * H)).astype(np.float32))
+            P.append((O.lstm_bias_init(H) + 0.1 * rng.randn(4 * H)).astype(np.float32))
+        Din = ndir * H
+    names.append('global/encoder/output/W')
+    P.append(rng.uniform(-1.85, 1.85, (ndir * H, F * E)).astype(np.float32))
+    dembed = cu(rng.randn(B, T, F * E).astype(np.float32))
+    xg = cu(x)
+
+    def step():
+        Pc = [cu(p).requires_grad_(True) for p in P]              # fresh leaves: the gradients come back through autograd
+        embed = ops.RnnEncoderFn.apply(xg, H, L, ndir, *Pc)
+        embed.backward(dembed)
+        torch.cuda.synchronize()
+        return [embed.detach()] + [p.grad for p in Pc]
+    first, again = step(), step()
+    monkeypatch.setattr(ops, 'ENC_PROLOGUE', False)
+    off = step()
+    what = ['embed'] + names
+    assert [n for n, a, b in zip(what, first, again) if not torch.equal(a, b)] == [], 'the step is not reproducible'
+    assert [n for n, a, b in zip(what, first, off) if not torch.equal(a, b)] == [], 'the switch changes bits'
+    Pt = {n: torch.tensor(p, dtype=torch.float64, requires_grad=True) for n, p in zip(names, P)}
+    with oracle_threads():
+        ref = (R.bilstm_encoder if ndir == 2 else R.lstm_encoder)(torch.tensor(x, dtype=torch.float64), Pt, H, L, E)
+        (ref.reshape(B, T, F * E) * dembed.cpu().double()).sum().backward()
+    e_out = relerr(off[0].cpu().numpy(), ref.detach().reshape(B, T, F * E).numpy())
+    errs = {n: relerr(g.cpu().numpy(), Pt[n].grad.numpy()) for n, g in zip(names, off[1:])}
+    print('encoder B %d T %d H %d ndir %d: embed %.3g, worst gradient %s' % (
+        B, T, H, ndir, e_out, max(errs.items(), key=lambda kv: kv[1])))
+    assert e_out < TOL
+    bad = {k: v for k, v in errs.items() if not v < GTOL}
+    assert not bad, bad
+
+
 # ---------------------------------------------------------------- frontend
 def test_frontend_and_reattach():
     from danet_amd import ops
