@@ -417,6 +417,108 @@ def istft(X, stride, window):
     return out[0] if squeeze else out
 
 
+# ---- the wrappers of the extension libraries: what they share ------------------------------------------
+# A new library's wrapper checks every tensor it hands to the library with _chk (or takes its `out` from _out, which
+# allocates or checks), and a chain that keeps intermediates between launches gets them from _scratch: it lists its
+# parts as [(name, shape, dtype)] in the order of the header's layout, names the library's *_workspace_bytes, and keeps
+# a dict of its own as the per-shape cache.  Nothing else carves a buffer or keys a cache by (device, stream).
+def _dev_index(dev):
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def _stride(fft_stride):
+    '''the hop of the STFT: hparams.FFT_STRIDE unless given'''
+    from .hparams import hparams
+    return int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
+
+
+def _chk(name, t, dtype, shape=None, numel=None, dim=None, dev=None, contiguous=True, cuda=True, optional=False):
+    '''t, an argument called `name`, is a tensor of `dtype` and, where asked, of this exact shape, numel, dim and
+    device; contiguous and on a GPU unless the call says otherwise; None only where `optional` -> t, else an
+    AssertionError naming the argument, what was wanted and what was got'''
+    if t is None and optional:
+        return t
+    if not (torch.is_tensor(t) and t.dtype == dtype and (t.is_cuda or not cuda)
+            and (shape is None or tuple(t.shape) == tuple(shape)) and (numel is None or t.numel() == numel)
+            and (dim is None or t.dim() == dim) and (dev is None or t.device == dev)
+            and (not contiguous or t.is_contiguous())):
+        want = [str(dtype)] + ['%s %s' % kv for kv in (('shape', shape if shape is None else tuple(shape)),
+                                                       ('numel', numel), ('dim', dim), ('on', dev)) if kv[1] is not None]
+        got = '%s %s, strides %s, on %s' % (t.dtype, tuple(t.shape), t.stride(), t.device) if torch.is_tensor(t) else repr(t)
+        raise AssertionError('%s: want %s%s%s, got %s' % (name, ', '.join(want), ', contiguous' if contiguous else '',
+                                                          ', on a GPU' if cuda else '', got))
+    return t
+
+
+def _out(name, out, shape, dtype, dev):
+    '''`out`, checked to be of this shape and dtype on `dev`, or a fresh tensor when it is None'''
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    return _chk(name, out, dtype, shape, dev=dev)
+
+
+def _result(B, k, dev, flags=False, count=False):
+    '''the tensors a finalize launch writes for a batch of B utterances and k figures: (per_utt float64 [B, k],
+    perm_idx int32 [B], [flags int32 [B],] means float64 [k], [count int32 [1]])'''
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    return (torch.empty(B, k, dtype=torch.float64, device=dev), i32(B)) + ((i32(B),) if flags else ()) \
+        + (torch.empty(k, dtype=torch.float64, device=dev),) + ((i32(1),) if count else ())
+
+
+def _check_result(per_utt, perm_idx, flags, means, k):
+    '''the (per_utt, perm_idx, flags, means) of a batch of any size, as _result lays them out -> its rows B_all'''
+    B_all = per_utt.shape[0]
+    _chk('per_utt', per_utt, torch.float64, (B_all, k), cuda=False)
+    _chk('perm_idx', perm_idx, torch.int32, (B_all,), cuda=False)
+    _chk('flags', flags, torch.int32, (B_all,), cuda=False)
+    _chk('means', means, torch.float64, numel=k, cuda=False)
+    return B_all
+
+
+def _group(B, limit, bytes_of):
+    '''the most utterances, at most B and limit // bytes_of(1) and at least one, whose scratch bytes_of(g) stays within
+    `limit`'''
+    g = max(1, min(int(B), limit // bytes_of(1)))
+    while g > 1 and bytes_of(g) > limit:
+        g -= 1
+    return g
+
+
+def _carve(buf, parts):
+    '''({name: view}, end): the parts [(name, shape, dtype)] laid into the uint8 buffer `buf` in their order, each at
+    the next multiple of 256 bytes, and the offset behind the last one, rounded up likewise.  buf None: no views, only
+    the end.  Works on any device.'''
+    views, off = {}, 0
+    for name, shape, dtype in parts:
+        n = int(np.prod(shape)) * dtype.itemsize
+        if buf is not None:
+            views[name] = buf[off:off + n].view(dtype).view(shape)
+        off += (n + 255) & ~255
+    return views, off
+
+
+def _scratch(tag, cache, dims, parts, nbytes, dev, flat=False):
+    '''(buffer, {name: view}), or with `flat` (buffer, view, view, ...): the parts() one shape `dims` cuts out of the
+    grow-only scratch `tag` of this (device, stream), cached in `cache` per (device, stream, shape); a hit returns the
+    cached tuple itself.  A hit counts only while its buffer is still the one _lib.workspace holds: a larger shape may
+    have replaced it.  nbytes(): the library's size of the layout, which the carve must end at; None where the layout
+    is the caller's own and the carve's end is the size.'''
+    key = (_dev_index(dev), torch.cuda.current_stream().cuda_stream) + tuple(dims)
+    hit = cache.get(key)
+    if hit is not None and _lib._ws.get(key[:2] + (tag,)) is hit[0]:
+        return hit
+    want = None if nbytes is None else nbytes()            # first: the library refuses a shape outside its envelope
+    parts = parts()
+    end = _carve(None, parts)[1]
+    assert want is None or end == want, (tag, end, want)
+    buf = _lib.workspace(end, dev, tag)
+    if len(cache) >= 64:
+        cache.clear()
+    views = _carve(buf, parts)[0]
+    hit = cache[key] = (buf,) + tuple(views.values()) if flat else (buf, views)
+    return hit
+
+
 # ---- ragged-batch STFT of the wavdir dataset (include/danet_prep_hip.h) ----------------------------
 # On the extension library libdanet_prep_hip.so, mapped at the first call.  ops.stft above stays the
 # front-end of every other path.
@@ -509,7 +611,7 @@ def prep_desc(offsets, lengths, pad_left, T_out, pool_len, fft_size, fft_stride,
 
 def _prep_plan(window, fft_size):
     '''the (device, N, window) plan: twiddles + 1/sum(window), built once by danet_prep_stft_plan'''
-    dev = window.device.index if window.device.index is not None else torch.cuda.current_device()
+    dev = _dev_index(window.device)
     fast = (dev, fft_size, window.data_ptr(), window._version)
     hit = _prep_plans_fast.get(fast)
     if hit is not None:
@@ -535,9 +637,8 @@ def stft_batch(pool, desc, T_out, window, fft_size, fft_stride, t_begin=0, t_cou
     a numpy record array (validated again and uploaded here) or a device uint8 / int64 tensor of 24-byte
     rows the caller has validated and uploaded.  window: float32 device vector.  out: optional
     complex64 [n_utt, t_count, >= F] view whose last dimension is contiguous (its row pitch is used).'''
-    assert pool.is_cuda and pool.dtype == torch.float32 and pool.dim() == 1 and pool.is_contiguous()
-    window = _f32(window)
-    assert window.device == pool.device and window.numel() == fft_size
+    _chk('pool', pool, torch.float32, dim=1)
+    _chk('window', window, torch.float32, numel=fft_size, dev=pool.device, contiguous=False)
     if t_count is None:
         t_count = T_out - t_begin
     F = fft_size // 2 + 1
@@ -545,7 +646,7 @@ def stft_batch(pool, desc, T_out, window, fft_size, fft_stride, t_begin=0, t_cou
         d['offset'], d['length'], d['pad_left'], T_out, pool.numel(), fft_size, fft_stride), pool.device)
     if out is None:
         out = torch.empty(n_utt, t_count, F, dtype=torch.complex64, device=pool.device)
-    assert out.dtype == torch.complex64 and out.is_cuda and tuple(out.shape) == (n_utt, t_count, F), out.shape
+    _chk('out', out, torch.complex64, (n_utt, t_count, F), contiguous=False)
     ld = _c64_row_pitch(out, F)
     plan = _prep_plan(window, fft_size)
     with _lib.timed('stft_batch'):
@@ -564,12 +665,10 @@ def mix_power(pool, offsets, lengths, max_len=None):
     offsets, lengths: host integer sequences (validated here: a row outside the pool is a ValueError
     before any upload or launch) or int64 device tensors the caller has validated (the kernel clamps,
     and `max_len`, an upper bound of the lengths, must then be given).'''
-    assert pool.is_cuda and pool.dtype == torch.float32 and pool.dim() == 1 and pool.is_contiguous()
+    _chk('pool', pool, torch.float32, dim=1)
     offsets, lengths, max_len = _row_tables('mix_power', pool, offsets, lengths, max_len)
-    for t in (offsets, lengths):
-        assert t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous()
-    n = offsets.numel()
-    assert lengths.numel() == n
+    n = _chk('offsets', offsets, torch.int64, dim=1).numel()
+    _chk('lengths', lengths, torch.int64, numel=n, dim=1)
     L = _lib.load_mix()
     nbytes = _lib.bytes_or_raise(L.danet_mix_workspace_bytes(n, int(max_len)), _lib.mix_check)
     ws = _lib.workspace(nbytes, pool.device, 'mix') if nbytes else None
@@ -584,10 +683,9 @@ def mix_scale_(batch, gains):
     '''batch[u] *= gains[u] in place, ONE launch (danet_mix_scale_c64): complex64 device tensor
     [n_utt, t_count, F] whose last dimension is contiguous (its row pitch is used; the gaps are never
     touched), float32 device vector [n_utt].  Every part becomes the single rounding fl(g * x).'''
-    assert batch.is_cuda and batch.dtype == torch.complex64 and batch.dim() == 3, (batch.dtype, batch.shape)
+    _chk('batch', batch, torch.complex64, dim=3, contiguous=False)
     n_utt, t_count, F = batch.shape
-    assert gains.is_cuda and gains.dtype == torch.float32 and gains.dim() == 1 and gains.is_contiguous()
-    assert gains.numel() == n_utt and gains.device == batch.device
+    _chk('gains', gains, torch.float32, (n_utt,), dev=batch.device)
     ld = _c64_row_pitch(batch, F)
     with _lib.timed('mix_scale'):
         _lib.mix_check(_lib.load_mix().danet_mix_scale_c64(
@@ -610,7 +708,7 @@ def level_activity(pool, offsets, lengths, thresholds, g, hang, max_len=None):
     before any upload or launch) or int64 device tensors the caller has validated (the kernel clamps,
     and `max_len`, an upper bound of the lengths, must then be given).  thresholds: float64 [n, 16], a host
     array or a device tensor.  Every violation the host can see is a ValueError raised before any launch.'''
-    assert pool.is_cuda and pool.dtype == torch.float32 and pool.dim() == 1 and pool.is_contiguous()
+    _chk('pool', pool, torch.float32, dim=1)
     g, hang = float(g), int(hang)
     if not 0.0 < g < 1.0:
         raise ValueError('level_activity: g must be inside (0, 1), got %r' % (g,))
@@ -618,9 +716,8 @@ def level_activity(pool, offsets, lengths, thresholds, g, hang, max_len=None):
         raise ValueError('level_activity: hang must be in [0, 2^40] samples, got %r' % (hang,))
     offsets, lengths, max_len = _row_tables('level_activity', pool, offsets, lengths, max_len)
     max_len = int(max_len)
-    for t in (offsets, lengths):
-        assert t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous()
-    n = offsets.numel()
+    n = _chk('offsets', offsets, torch.int64, dim=1).numel()
+    _chk('lengths', lengths, torch.int64, dim=1)
     if n < 1 or lengths.numel() != n:
         raise ValueError('level_activity: offsets and lengths must be two vectors of one length >= 1')
     if not torch.is_tensor(thresholds):
@@ -703,10 +800,9 @@ def speed_resample(pool, desc, table, out):
     is touched.  desc: the table of ops.speed_desc -- a numpy record array (validated again and uploaded
     here) or a device uint8 / int64 tensor of 40-byte rows the caller has validated and uploaded.
     table: ops.speed_table(P) on the device, float32 [512, 32].  There is no CPU fallback.'''
-    for t in (pool, out):
-        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()
-    assert table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()
-    assert tuple(table.shape) == (SPEED_PHASES, SPEED_TAPS) and table.device == pool.device == out.device
+    _chk('pool', pool, torch.float32, dim=1)
+    _chk('out', out, torch.float32, dim=1, dev=pool.device)
+    _chk('table', table, torch.float32, (SPEED_PHASES, SPEED_TAPS), dev=pool.device)
     desc, n_utt = _desc_table('speed_resample', 'SPEED_DESC_DTYPE', desc, lambda d: speed_desc(
         d['src_offset'], d['src_length'], d['dst_offset'], d['dst_length'], d['p'], pool.numel(), out.numel()),
         pool.device)
@@ -794,10 +890,9 @@ def reverb_apply(src, desc, bank, n_taps, out):
     spans is touched.  desc: the table of ops.reverb_desc -- a numpy record array (validated again and uploaded
     here) or a device uint8 / int64 tensor of 48-byte rows the caller has validated and uploaded.
     bank: ops.reverb_bank(R, smprate) on the device, float32 [32, n_taps].  There is no CPU fallback.'''
-    for t in (src, out):
-        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()
-    assert bank.is_cuda and bank.dtype == torch.float32 and bank.is_contiguous()
-    assert tuple(bank.shape) == (REVERB_ROWS, n_taps) and bank.device == src.device == out.device
+    _chk('src', src, torch.float32, dim=1)
+    _chk('out', out, torch.float32, dim=1, dev=src.device)
+    _chk('bank', bank, torch.float32, (REVERB_ROWS, n_taps), dev=src.device)
     assert src.data_ptr() != out.data_ptr()
     desc, n_utt = _desc_table('reverb_apply', 'REVERB_DESC_DTYPE', desc, lambda d: reverb_desc(
         d['src_offset'], d['src_length'], d['dst_offset'], d['out_begin'], d['out_count'], d['row'], src.numel(),
@@ -812,7 +907,7 @@ def reverb_apply(src, desc, bank, n_taps, out):
 # On the extension library libdanet_metric_hip.so, mapped at the first call: a run with EVAL_SI_SDR null never
 # gets here.  Three launches: spectra -> waveforms -> Gram matrices -> decibels.
 METRIC_MAX_C = 4                                     # DANET_METRIC_MAX_C
-_metric_ws = {}          # (device index, stream, B, C, T, N, S) -> (scratch, wav, G, per_utt, mean2, perm_idx)
+_metric_ws = {}          # (device index, stream, B, C, T, N, S) -> (scratch, wav, G, per_utt, mean2, perm_idx): a cache of _scratch
 _metric_windows = {}     # (device index, window bytes) -> float32 device vector
 
 
@@ -820,51 +915,49 @@ def _metric_window(dev):
     '''hparams.FFT_WND as a float32 device vector, uploaded once per (device, window)'''
     from .hparams import hparams
     w = np.ascontiguousarray(np.asarray(hparams.FFT_WND, dtype=np.float32))
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), w.tobytes())
+    key = (_dev_index(dev), w.tobytes())
     t = _metric_windows.get(key)
     if t is None:
         t = _metric_windows[key] = torch.from_numpy(w.copy()).to(dev)
     return t
 
 
+_WAVE = {'metric': (_lib.load_metric, _lib.metric_check), 'neval': (_lib.load_neval, _lib.neval_check)}
+
+
+def _wave_fn(tag, name):
+    '''(danet_<tag>_<name> of the library of that tag (metric or neval), that library's check)'''
+    load, check_ = _WAVE[tag]
+    return getattr(load(), 'danet_%s_%s' % (tag, name)), check_
+
+
 def _wave_call(tag, name, *args):
-    '''danet_<tag>_<name>(*args) on the library of that tag (metric or neval), its status checked'''
-    lib = getattr(_lib, 'load_' + tag)()
-    getattr(_lib, tag + '_check')(getattr(lib, 'danet_%s_%s' % (tag, name))(*args))
+    '''danet_<tag>_<name>(*args), its status checked'''
+    fn, check_ = _wave_fn(tag, name)
+    check_(fn(*args))
+
+
+def _wave_parts(rows, outs, B, T, S):
+    '''[(name, shape, dtype)] of the parts of the buffer of danet_<tag>_workspace_bytes, in its order: `rows` signals
+    and `outs` figures per utterance'''
+    f64 = torch.float64
+    return [('wav', (B, rows, (T - 1) * S), torch.float32), ('G', (B, rows, rows), f64), ('per_utt', (B, outs), f64),
+            ('means', (outs,), f64), ('perm_idx', (B,), torch.int32)]
 
 
 def _wave_workspace(tag, cache, rows, outs, B, C, T, N, S, dev):
     '''(buffer, wav, G, per_utt, means, perm_idx): the views one shape cuts out of the grow-only scratch `tag` of this
-    (device, stream), in the layout of danet_<tag>_workspace_bytes -- `rows` signals and `outs` figures per
-    utterance; cached per shape in `cache`'''
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
-           torch.cuda.current_stream().cuda_stream, B, C, T, N, S)
-    hit = cache.get(key)
-    if hit is not None and _lib._ws.get(key[:2] + (tag,)) is hit[0]:
-        return hit
-    nbytes = _lib.bytes_or_raise(
-        getattr(getattr(_lib, 'load_' + tag)(), 'danet_%s_workspace_bytes' % tag)(B, C, T, N, S), getattr(_lib, tag + '_check'))
-    buf = _lib.workspace(nbytes, dev, tag)
-    Ls = (T - 1) * S
-    views, off = [], 0
-    for shape, dtype, size in (((B, rows, Ls), torch.float32, 4), ((B, rows, rows), torch.float64, 8),
-                               ((B, outs), torch.float64, 8), ((outs,), torch.float64, 8), ((B,), torch.int32, 4)):
-        n = int(np.prod(shape)) * size
-        views.append(buf[off:off + n].view(dtype).view(shape))
-        off += (n + 255) & ~255
-    assert off == nbytes, (off, nbytes)
-    if len(cache) >= 64:
-        cache.clear()
-    hit = cache[key] = (buf,) + tuple(views)
-    return hit
+    (device, stream), in the layout of danet_<tag>_workspace_bytes; cached per shape in `cache`'''
+    def nbytes():
+        fn, check_ = _wave_fn(tag, 'workspace_bytes')
+        return _lib.bytes_or_raise(fn(B, C, T, N, S), check_)
+    return _scratch(tag, cache, (B, C, T, N, S), lambda: _wave_parts(rows, outs, B, T, S), nbytes, dev, flat=True)
 
 
 def _wave_gram(tag, wav, out):
-    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.is_contiguous()
+    _chk('wav', wav, torch.float32, dim=3)
     B, M, Ls = wav.shape
-    if out is None:
-        out = torch.empty(B, M, M, dtype=torch.float64, device=wav.device)
-    assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B, M, M)
+    out = _out('out', out, (B, M, M), torch.float64, wav.device)
     with _lib.timed(tag + '_gram'):
         _wave_call(tag, 'gram', _lib.stream(), B, M, Ls, ptr(wav), ptr(out))
     return out
@@ -872,13 +965,10 @@ def _wave_gram(tag, wav, out):
 
 def _wave_finalize(tag, outs, G, out):
     '''G [B, M, M], M = 2C + outs - 2 -> (means [outs], per_utt [B, outs], perm_idx int32 [B])'''
-    assert G.is_cuda and G.dtype == torch.float64 and G.dim() == 3 and G.is_contiguous() and G.shape[1] == G.shape[2]
+    _chk('G', G, torch.float64, dim=3)
     B, M = G.shape[0], G.shape[1]
-    assert M % 2 == outs - 2, M
-    if out is None:
-        out = (torch.empty(B, outs, dtype=torch.float64, device=G.device),
-               torch.empty(B, dtype=torch.int32, device=G.device), torch.empty(outs, dtype=torch.float64, device=G.device))
-    per_utt, perm_idx, means = out
+    assert M == G.shape[2] and M % 2 == outs - 2, G.shape
+    per_utt, perm_idx, means = _result(B, outs, G.device) if out is None else out
     with _lib.timed(tag + '_si_sdr'):
         _wave_call(tag, 'si_sdr', _lib.stream(), B, M // 2, ptr(G), ptr(per_utt), ptr(perm_idx), ptr(means))
     return means, per_utt, perm_idx
@@ -888,16 +978,15 @@ def metric_synth(src, est, fft_stride, window=None, out=None):
     '''references and UNPERMUTED estimates, complex64 [B, C, T, F] -> float32 waveforms [B, 2C, (T - 1) * S],
     references first, ONE launch (danet_metric_synth: overlap-add with an exact window-sum division).
     window: float32 device vector [N] (default hparams.FFT_WND, uploaded once).'''
-    assert src.is_cuda and src.dtype == torch.complex64 and src.dim() == 4, (src.dtype, src.shape)
-    assert est.is_cuda and est.dtype == torch.complex64 and est.shape == src.shape and est.device == src.device
+    _chk('src', src, torch.complex64, dim=4, contiguous=False)
+    _chk('est', est, torch.complex64, src.shape, dev=src.device, contiguous=False)
     src, est = src.contiguous(), est.contiguous()
     B, C, T, F = src.shape
     N = 2 * (F - 1)
     window = _metric_window(src.device) if window is None else _f32(window).contiguous()
-    assert window.numel() == N and window.device == src.device, (window.numel(), N)
-    if out is None:
-        out = torch.empty(B, 2 * C, max(T - 1, 0) * fft_stride, dtype=torch.float32, device=src.device)
-    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, 2 * C, (T - 1) * fft_stride)
+    _chk('window', window, torch.float32, numel=N, dev=src.device)
+    assert T >= 1, T
+    out = _out('out', out, (B, 2 * C, (T - 1) * fft_stride), torch.float32, src.device)
     with _lib.timed('metric_synth'):
         _lib.metric_check(_lib.load_metric().danet_metric_synth(
             _lib.stream(), B, C, T, N, fft_stride, ptr(torch.view_as_real(src)), ptr(torch.view_as_real(est)),
@@ -929,17 +1018,13 @@ def si_sdr(src, est, fft_stride=None):
 def si_sdr_wav(src, est, fft_stride=None):
     '''si_sdr, and as a fifth result the waveforms it synthesised: float32 [B, 2C, (T - 1) * S], a VIEW of the cached
     scratch that the next call of this shape on this stream overwrites (ops.bss_eval reads it in the same step)'''
-    from .hparams import hparams
-    S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
+    S = _stride(fft_stride)
     B, C, T, F = src.shape
-    dev = src.device
-    ws = _wave_workspace('metric', _metric_ws, 2 * C, 2, B, C, T, 2 * (F - 1), S, dev)
+    ws = _wave_workspace('metric', _metric_ws, 2 * C, 2, B, C, T, 2 * (F - 1), S, src.device)
     wav, G = ws[1], ws[2]
     metric_synth(src, est, S, out=wav)
     metric_gram(wav, out=G)
-    mean2, per_utt, perm_idx = metric_finalize(G, out=(torch.empty(B, 2, dtype=torch.float64, device=dev),
-                                                       torch.empty(B, dtype=torch.int32, device=dev),
-                                                       torch.empty(2, dtype=torch.float64, device=dev)))
+    mean2, per_utt, perm_idx = metric_finalize(G, out=_result(B, 2, src.device))
     return mean2[0], mean2[1], per_utt, perm_idx, wav
 
 
@@ -947,8 +1032,7 @@ def synth_wav(src, est, fft_stride=None):
     '''the float32 waveforms [B, 2C, (T - 1) * S] of the references and the UNPERMUTED estimates, synthesised into the
     metric's cached scratch (a VIEW the next call of this shape on this stream overwrites): what ops.bss_eval and
     ops.stoi_eval synthesise for themselves when no `wav` is given, once for both'''
-    from .hparams import hparams
-    S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
+    S = _stride(fft_stride)
     B, C, T, F = src.shape
     wav = _wave_workspace('metric', _metric_ws, 2 * C, 2, B, C, T, 2 * (F - 1), S, src.device)[1]
     return metric_synth(src, est, S, out=wav)
@@ -958,7 +1042,7 @@ def synth_wav(src, est, fft_stride=None):
 # On the extension library libdanet_phase_hip.so, mapped at the first call: a run with PHASE_REFINE_ITERS null never
 # gets here.  init (two launches), then per iteration: waveforms of the iterate -> projection onto the magnitudes.
 PHASE_MAX_C = 4                                      # DANET_PHASE_MAX_C
-_phase_ws = {}           # (device index, stream, B, C, T, N, S) -> the workspace buffer
+_phase_ws = {}           # (device index, stream, B, C, T, N, S) -> (scratch, views)
 
 
 def phase_workspace_bytes(B, C, T, N, S):
@@ -970,37 +1054,29 @@ def phase_workspace_bytes(B, C, T, N, S):
 def phase_parts(ws, B, C, T, N, S):
     '''(A float32 [B, C, T, F], mix complex64 [B, T, F], wav float32 [B, C + 1, Ls]): views of the three parts of a
     workspace buffer (uint8, at least phase_workspace_bytes long) in the header's layout'''
-    F, Ls = N // 2 + 1, (T - 1) * S
-    views, off = [], 0
-    for shape, dtype, size in (((B, C, T, F), torch.float32, 4), ((B, T, F), torch.complex64, 8),
-                               ((B, C + 1, Ls), torch.float32, 4)):
-        n = int(np.prod(shape)) * size
-        views.append(ws[off:off + n].view(dtype).view(shape))
-        off += (n + 255) & ~255
-    return tuple(views)
+    return tuple(_carve(ws, _phase_layout(B, C, T, N, S))[0].values())
+
+
+def _phase_layout(B, C, T, N, S):
+    '''[(name, shape, dtype)] of the parts of the buffer of danet_phase_workspace_bytes, in its order'''
+    F = N // 2 + 1
+    return [('A', (B, C, T, F), torch.float32), ('mix', (B, T, F), torch.complex64),
+            ('wav', (B, C + 1, (T - 1) * S), torch.float32)]
 
 
 def _phase_workspace(B, C, T, N, S, dev):
     '''the grow-only scratch 'phase' of this (device, stream), at least one workspace of this shape long; its size
     is asked of the library once per shape'''
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
-           torch.cuda.current_stream().cuda_stream, B, C, T, N, S)
-    hit = _phase_ws.get(key)
-    if hit is not None and _lib._ws.get(key[:2] + ('phase',)) is hit:
-        return hit
-    if len(_phase_ws) >= 64:
-        _phase_ws.clear()
-    hit = _phase_ws[key] = _lib.workspace(phase_workspace_bytes(B, C, T, N, S), dev, 'phase')
-    return hit
+    return _scratch('phase', _phase_ws, (B, C, T, N, S), lambda: _phase_layout(B, C, T, N, S),
+                    lambda: phase_workspace_bytes(B, C, T, N, S), dev)[0]
 
 
 def _phase_args(x, window, ws, fft_stride):
-    assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 4 and x.is_contiguous(), (x.dtype, x.shape)
+    _chk('x', x, torch.complex64, dim=4)
     B, C, T, F = x.shape
     N = 2 * (F - 1)
-    assert window.is_cuda and window.dtype == torch.float32 and window.is_contiguous() and window.numel() == N \
-        and window.device == x.device, (window.shape, N)
-    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == x.device
+    _chk('window', window, torch.float32, numel=N, dev=x.device)
+    _chk('ws', ws, torch.uint8, dev=x.device)
     S = int(fft_stride)
     assert ws.numel() >= phase_workspace_bytes(B, C, T, N, S), ws.numel()
     return B, C, T, N, S
@@ -1012,11 +1088,9 @@ def phase_init(est0, mixrows, window, ws, fft_stride, x=None):
     if x is None:
         x = torch.empty_like(est0)
     B, C, T, N, S = _phase_args(x, window, ws, fft_stride)
-    assert est0.is_cuda and est0.dtype == torch.complex64 and est0.is_contiguous() and est0.shape == x.shape \
-        and est0.device == x.device, (est0.dtype, est0.shape)
-    assert mixrows.is_cuda and mixrows.dtype == torch.complex64 and mixrows.dim() == 4 and mixrows.is_contiguous() \
-        and mixrows.device == x.device and (mixrows.shape[0],) + tuple(mixrows.shape[2:]) == (B, T, N // 2 + 1), \
-        (mixrows.dtype, mixrows.shape)
+    _chk('est0', est0, torch.complex64, x.shape, dev=x.device)
+    _chk('mixrows', mixrows, torch.complex64, dim=4, dev=x.device)
+    assert (mixrows.shape[0],) + tuple(mixrows.shape[2:]) == (B, T, N // 2 + 1), mixrows.shape
     with _lib.timed('phase_init'):
         _lib.phase_check(_lib.load_phase().danet_phase_init(
             _lib.stream(), B, C, mixrows.shape[1], T, N, S, ptr(torch.view_as_real(est0)),
@@ -1037,8 +1111,7 @@ def phase_project(x, window, ws, fft_stride, z_out=None):
     PLACE; z_out (complex64, the shape of x) receives the analysis Z when given -> x'''
     B, C, T, N, S = _phase_args(x, window, ws, fft_stride)
     if z_out is not None:
-        assert z_out.is_cuda and z_out.dtype == torch.complex64 and z_out.is_contiguous() and z_out.shape == x.shape \
-            and z_out.device == x.device and z_out.data_ptr() != x.data_ptr(), (z_out.dtype, z_out.shape)
+        assert _chk('z_out', z_out, torch.complex64, x.shape, dev=x.device).data_ptr() != x.data_ptr()
     with _lib.timed('phase_project'):
         _lib.phase_check(_lib.load_phase().danet_phase_project(
             _lib.stream(), B, C, T, N, S, ptr(window), ptr(ws), ptr(torch.view_as_real(x)),
@@ -1051,11 +1124,10 @@ def phase_refine(est0, mixrows, K, fft_stride=None, window=None):
     [B, Cm, T, F] -> complex64 [B, C, T, F], a FRESH tensor with the magnitudes of est0 (K = 0: est0 bit for bit).
     The workspace is a scratch cached per shape; 2 + 2K launches and nothing else on the device, no host
     synchronisation.  window: float32 device vector [N] (default hparams.FFT_WND, uploaded once).'''
-    from .hparams import hparams
-    S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
+    S = _stride(fft_stride)
     K = int(K)
     assert K >= 0, K
-    assert est0.is_cuda and est0.dtype == torch.complex64 and est0.dim() == 4, (est0.dtype, est0.shape)
+    _chk('est0', est0, torch.complex64, dim=4, contiguous=False)
     est0, mixrows = est0.contiguous(), mixrows.contiguous()
     B, C, T, F = est0.shape
     dev = est0.device
@@ -1085,7 +1157,7 @@ def online_state_bytes(C, E):
 def online_state_parts(state, C, E):
     '''(S [B, C, E], n [B, C], A [B, C, E]): views of a state tensor float64 [B, 2 C E + C] in the header's layout'''
     B, CE = state.shape[0], C * E
-    assert state.dtype == torch.float64 and state.shape == (B, 2 * CE + C), (state.dtype, state.shape)
+    _chk('state', state, torch.float64, (B, 2 * CE + C), contiguous=False, cuda=False)
     return state[:, :CE].view(B, C, E), state[:, CE:CE + C], state[:, CE + C:].view(B, C, E)
 
 
@@ -1096,8 +1168,7 @@ def online_init(a0, state=None):
     B, C, E = a0.shape
     if state is None:
         state = torch.empty(B, online_state_bytes(C, E) // 8, dtype=torch.float64, device=a0.device)
-    assert state.is_cuda and state.dtype == torch.float64 and state.is_contiguous() and state.device == a0.device \
-        and state.shape == (B, 2 * C * E + C), (state.dtype, state.shape)
+    _chk('state', state, torch.float64, (B, 2 * C * E + C), dev=a0.device)
     with _lib.timed('online_init'):
         _lib.online_check(_lib.load_online().danet_online_init(_lib.stream(), B, C, E, ptr(a0), ptr(state)))
     return state
@@ -1107,16 +1178,12 @@ def online_scan(embed, w, state, act, lam, T0, eps, t_first=0, attr=None):
     '''danet_online_scan, ONE launch: the frames t_first .. t_first + T - 1 of embed float32 [B, T, F, E] with the
     weights w float32 [B, T, F], from `state` (float64 [B, 2 C E + C], updated IN PLACE) -> the trajectory attr float32
     [B, T, C, E]'''
-    assert embed.dim() == 4 and embed.is_contiguous() and w.is_contiguous(), (embed.shape, w.shape)
-    embed, w = _f32(embed), _f32(w)
-    B, T, F, E = embed.shape
-    assert tuple(w.shape) == (B, T, F) and w.device == embed.device, (w.shape, embed.shape)
-    assert state.is_cuda and state.dtype == torch.float64 and state.is_contiguous() and state.device == embed.device \
-        and state.dim() == 2 and state.shape[0] == B and (state.shape[1] % (2 * E + 1)) == 0, (state.dtype, state.shape)
+    B, T, F, E = _chk('embed', embed, torch.float32, dim=4).shape
+    _chk('w', w, torch.float32, (B, T, F), dev=embed.device)
+    _chk('state', state, torch.float64, dim=2, dev=embed.device)
+    assert state.shape[0] == B and (state.shape[1] % (2 * E + 1)) == 0, state.shape
     C = state.shape[1] // (2 * E + 1)
-    if attr is None:
-        attr = torch.empty(B, T, C, E, device=embed.device)
-    assert _f32(attr).is_contiguous() and tuple(attr.shape) == (B, T, C, E) and attr.device == embed.device, attr.shape
+    attr = _out('attr', attr, (B, T, C, E), torch.float32, embed.device)
     with _lib.timed('online_scan'):
         _lib.online_check(_lib.load_online().danet_online_scan(
             _lib.stream(), B, C, T, F, E, int(act), float(lam), int(T0), int(t_first), float(eps), ptr(embed), ptr(w),
@@ -1132,9 +1199,7 @@ def online_separate(w, attr, embed, act, out=None):
     assert attr.dim() == 4 and tuple(attr.shape[:2]) == (B, T), (attr.shape, w.shape)
     C, E = attr.shape[2], attr.shape[3]
     assert embed.numel() == B * T * F * E and embed.shape[0] == B and embed.shape[-1] == E, (embed.shape, w.shape)
-    if out is None:
-        out = torch.empty(B, C, T, F, device=w.device)
-    assert _f32(out).is_contiguous() and tuple(out.shape) == (B, C, T, F) and out.device == w.device, out.shape
+    out = _out('out', out, (B, C, T, F), torch.float32, w.device)
     with _lib.timed('online_separate'):
         _lib.online_check(_lib.load_online().danet_online_separate(
             _lib.stream(), int(act), B, C, T, F, E, ptr(w), ptr(attr), ptr(embed), ptr(out)))
@@ -1166,8 +1231,7 @@ def causal_center_state(B, dev):
 def causal_center_fwd(x, B, T, D, in_layout, ld_in, out, out_layout, ld_out, state):
     '''danet_causal_center_fwd, ONE launch: out[t] = x[t] - the mean of everything up to and including frame t, from
     `state` (float64 [B, 2], updated IN PLACE); layouts as for `center`'''
-    assert state.is_cuda and state.dtype == torch.float64 and state.is_contiguous() and tuple(state.shape) == (B, 2), \
-        (state.dtype, state.shape)
+    _chk('state', state, torch.float64, (B, 2))
     with _lib.timed('causal_center'):
         _lib.causal_check(_lib.load_causal().danet_causal_center_fwd(
             _lib.stream(), B, T, D, ptr(_f32(x)), in_layout, ld_in, ptr(_f32(out)), out_layout, ld_out, ptr(state)))
@@ -1235,7 +1299,7 @@ def causal_project(A, M, K, N, lda, W, ldw, out=None, ldo=None):
 BSS_MAX_C = 4                                        # DANET_BSS_MAX_C
 BSS_MAX_L = 512                                      # DANET_BSS_MAX_L
 BSS_SCRATCH_BYTES = 256 << 20
-_bss_ws = {}             # (device index, stream, g, C, L) -> (scratch, R, D, ee, G, Gs, Xg, Xs, fg, fs)
+_bss_ws = {}             # (device index, stream, g, C, L) -> (scratch, views)
 
 
 def bss_workspace_bytes(B, C, L):
@@ -1255,43 +1319,19 @@ def bss_parts(B, C, L):
 def _bss_workspace(g, C, L, dev):
     '''the views a group of g utterances cuts out of the grow-only scratch 'bss' of this (device, stream): a dict by
     the names of bss_parts; cached per shape'''
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
-           torch.cuda.current_stream().cuda_stream, g, C, L)
-    hit = _bss_ws.get(key)
-    if hit is not None and _lib._ws.get(key[:2] + ('bss',)) is hit[0]:
-        return hit[1]
-    nbytes = bss_workspace_bytes(g, C, L)
-    buf = _lib.workspace(nbytes, dev, 'bss')
-    views, off = {}, 0
-    for name, shape, dtype in bss_parts(g, C, L):
-        n = int(np.prod(shape)) * (8 if dtype == torch.float64 else 4)
-        views[name] = buf[off:off + n].view(dtype).view(shape)
-        off += (n + 255) & ~255
-    assert off == nbytes, (off, nbytes)
-    if len(_bss_ws) >= 64:
-        _bss_ws.clear()
-    _bss_ws[key] = (buf, views)
-    return views
-
-
-def _bss_out(out, shape, dtype, dev):
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=dev)
-    assert out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == tuple(shape), \
-        (out.dtype, out.shape, shape)
-    return out
+    return _scratch('bss', _bss_ws, (g, C, L), lambda: bss_parts(g, C, L), lambda: bss_workspace_bytes(g, C, L), dev)[1]
 
 
 def bss_xcorr(wav, filter_len, out=None):
     '''float32 waveforms [B, 2C, Ls] (references first) -> (R [B, C, C, 2L - 1], D [B, C, C, L], ee [B, C]), float64,
     ONE launch (danet_bss_xcorr); out: optional (R, D, ee) to write into'''
-    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.is_contiguous() and wav.shape[1] % 2 == 0
-    B, M, Ls = wav.shape
+    B, M, Ls = _chk('wav', wav, torch.float32, dim=3).shape
+    assert M % 2 == 0, M
     C, L, dev = M // 2, int(filter_len), wav.device
     out = out or (None, None, None)
-    R = _bss_out(out[0], (B, C, C, 2 * L - 1), torch.float64, dev)
-    D = _bss_out(out[1], (B, C, C, L), torch.float64, dev)
-    ee = _bss_out(out[2], (B, C), torch.float64, dev)
+    R = _out('R', out[0], (B, C, C, 2 * L - 1), torch.float64, dev)
+    D = _out('D', out[1], (B, C, C, L), torch.float64, dev)
+    ee = _out('ee', out[2], (B, C), torch.float64, dev)
     with _lib.timed('bss_xcorr'):
         _lib.bss_check(_lib.load_bss().danet_bss_xcorr(_lib.stream(), B, C, Ls, L, ptr(wav), ptr(R), ptr(D), ptr(ee)))
     return R, D, ee
@@ -1300,15 +1340,14 @@ def bss_xcorr(wav, filter_len, out=None):
 def bss_systems(R, D, out=None):
     '''R [B, C, C, 2L - 1], D [B, C, C, L] -> (G [B, CL, CL], Gs [B, C, L, L], Xg [B, C, CL], Xs [B, C, C + 1, L]),
     ONE launch (danet_bss_systems); out: optional tuple of the four to write into'''
-    assert R.is_cuda and R.dtype == torch.float64 and R.dim() == 4 and R.is_contiguous()
-    B, C, L, dev = R.shape[0], R.shape[1], D.shape[3], R.device
-    assert tuple(R.shape) == (B, C, C, 2 * L - 1) and D.dtype == torch.float64 and D.is_contiguous() \
-        and tuple(D.shape) == (B, C, C, L) and D.device == dev, (R.shape, D.shape)
+    B, C, L, dev = _chk('R', R, torch.float64, dim=4).shape[0], R.shape[1], D.shape[3], R.device
+    _chk('R', R, torch.float64, (B, C, C, 2 * L - 1))
+    _chk('D', D, torch.float64, (B, C, C, L), dev=dev)
     out = out or (None,) * 4
-    G = _bss_out(out[0], (B, C * L, C * L), torch.float64, dev)
-    Gs = _bss_out(out[1], (B, C, L, L), torch.float64, dev)
-    Xg = _bss_out(out[2], (B, C, C * L), torch.float64, dev)
-    Xs = _bss_out(out[3], (B, C, C + 1, L), torch.float64, dev)
+    G = _out('G', out[0], (B, C * L, C * L), torch.float64, dev)
+    Gs = _out('Gs', out[1], (B, C, L, L), torch.float64, dev)
+    Xg = _out('Xg', out[2], (B, C, C * L), torch.float64, dev)
+    Xs = _out('Xs', out[3], (B, C, C + 1, L), torch.float64, dev)
     with _lib.timed('bss_systems'):
         _lib.bss_check(_lib.load_bss().danet_bss_systems(_lib.stream(), B, C, L, ptr(R), ptr(D), ptr(G), ptr(Gs),
                                                          ptr(Xg), ptr(Xs)))
@@ -1319,11 +1358,10 @@ def bss_chol_solve(A, X, flags=None):
     '''IN PLACE: A float64 [nmat, n, n] symmetric positive definite -> its Cholesky factor, X float64 [nmat, nrhs, n]
     (one right-hand side per row) -> the solutions; -> flags int32 [nmat], 1 where a pivot failed
     (danet_bss_chol_solve: blocked, the trailing updates of the whole batch on f64 MFMA)'''
-    assert A.is_cuda and A.dtype == torch.float64 and A.dim() == 3 and A.is_contiguous() and A.shape[1] == A.shape[2]
-    nmat, n = A.shape[0], A.shape[1]
-    assert X.dtype == torch.float64 and X.dim() == 3 and X.is_contiguous() and X.device == A.device \
-        and X.shape[0] == nmat and X.shape[2] == n, (A.shape, X.shape)
-    flags = _bss_out(flags, (nmat,), torch.int32, A.device)
+    nmat, n = _chk('A', A, torch.float64, dim=3).shape[:2]
+    _chk('X', X, torch.float64, dim=3, dev=A.device)
+    assert A.shape[2] == n and X.shape[0] == nmat and X.shape[2] == n, (A.shape, X.shape)
+    flags = _out('flags', flags, (nmat,), torch.int32, A.device)
     with _lib.timed('bss_chol_solve'):
         _lib.bss_check(_lib.load_bss().danet_bss_chol_solve(_lib.stream(), nmat, n, X.shape[1], ptr(A), ptr(X),
                                                             ptr(flags)))
@@ -1336,20 +1374,13 @@ def bss_finalize(R, D, ee, Xg, Xs, fg, fs, b0=0, out=None):
     b0 + B - 1 are written, and mean4 from all rows when b0 + B = B_all.  out: optional (per_utt, perm_idx, flags,
     mean4) of a batch of B_all utterances to write into (default B_all = B)'''
     B, C, L, dev = R.shape[0], R.shape[1], D.shape[3], R.device
-    for t, shape, dtype in ((R, (B, C, C, 2 * L - 1), torch.float64), (D, (B, C, C, L), torch.float64),
-                            (ee, (B, C), torch.float64), (Xg, (B, C, C * L), torch.float64),
-                            (Xs, (B, C, C + 1, L), torch.float64), (fg, (B,), torch.int32), (fs, (B, C), torch.int32)):
-        assert t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, \
-            (t.dtype, t.shape, shape)
-    if out is None:
-        out = (torch.empty(B, 4, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.float64, device=dev))
-    per_utt, perm_idx, flags, mean4 = out
-    B_all = per_utt.shape[0]
-    assert per_utt.dtype == torch.float64 and per_utt.is_contiguous() and tuple(per_utt.shape) == (B_all, 4)
-    assert perm_idx.dtype == torch.int32 and perm_idx.is_contiguous() and tuple(perm_idx.shape) == (B_all,)
-    assert flags.dtype == torch.int32 and flags.is_contiguous() and tuple(flags.shape) == (B_all,)
-    assert mean4.dtype == torch.float64 and mean4.is_contiguous() and mean4.numel() == 4
+    for name, t, shape, dtype in (('R', R, (B, C, C, 2 * L - 1), torch.float64), ('D', D, (B, C, C, L), torch.float64),
+                                  ('ee', ee, (B, C), torch.float64), ('Xg', Xg, (B, C, C * L), torch.float64),
+                                  ('Xs', Xs, (B, C, C + 1, L), torch.float64), ('fg', fg, (B,), torch.int32),
+                                  ('fs', fs, (B, C), torch.int32)):
+        _chk(name, t, dtype, shape, dev=dev)
+    per_utt, perm_idx, flags, mean4 = _result(B, 4, dev, flags=True) if out is None else out
+    B_all = _check_result(per_utt, perm_idx, flags, mean4, 4)
     with _lib.timed('bss_finalize'):
         _lib.bss_check(_lib.load_bss().danet_bss_finalize(
             _lib.stream(), B, C, L, ptr(R), ptr(D), ptr(ee), ptr(Xg), ptr(Xs), ptr(fg), ptr(fs), int(b0), B_all,
@@ -1359,10 +1390,7 @@ def bss_finalize(R, D, ee, Xg, Xs, fg, fs, b0=0, out=None):
 
 def bss_group(B, C, L):
     '''the utterances ops.bss_eval takes at a time: the most whose scratch stays under BSS_SCRATCH_BYTES (one at least)'''
-    g = max(1, min(int(B), BSS_SCRATCH_BYTES // bss_workspace_bytes(1, C, L)))
-    while g > 1 and bss_workspace_bytes(g, C, L) > BSS_SCRATCH_BYTES:
-        g -= 1
-    return g
+    return _group(B, BSS_SCRATCH_BYTES, lambda g: bss_workspace_bytes(g, C, L))
 
 
 def bss_eval(src, est, filter_len=None, fft_stride=None, wav=None, group=None):
@@ -1381,13 +1409,10 @@ def bss_eval(src, est, filter_len=None, fft_stride=None, wav=None, group=None):
     B, C, T, F = src.shape
     dev = src.device
     if wav is None:
-        S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
-        wav = _wave_workspace('metric', _metric_ws, 2 * C, 2, B, C, T, 2 * (F - 1), S, dev)[1]
-        metric_synth(src, est, S, out=wav)
-    assert wav.is_cuda and wav.dtype == torch.float32 and wav.is_contiguous() and tuple(wav.shape[:2]) == (B, 2 * C)
+        wav = synth_wav(src, est, fft_stride)
+    assert tuple(_chk('wav', wav, torch.float32).shape[:2]) == (B, 2 * C), wav.shape
     g = bss_group(B, C, L) if group is None else max(1, min(int(group), B))
-    out = (torch.empty(B, 4, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-           torch.empty(B, dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.float64, device=dev))
+    out = _result(B, 4, dev, flags=True)
     for b0 in range(0, B, g):
         nb = min(g, B - b0)
         w = _bss_workspace(nb, C, L, dev)
@@ -1431,7 +1456,7 @@ def stoi_rate(smprate):
 def stoi_tables(smprate, dev):
     '''the inputs the library computes nothing of, uploaded once per (device, SMPRATE): h (float32 [2H + 1]), the
     window w (float32 [256]), the twiddle factors tw (float64 [256, 2]) and the band bins (a HOST int32 [15][2])'''
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(smprate))
+    key = (_dev_index(dev), int(smprate))
     t = _stoi_tables.get(key)
     if t is not None:
         return t
@@ -1483,53 +1508,41 @@ def stoi_parts(B, C, Ls, U, D):
 def _stoi_workspace(g, C, Ls, U, D, dev):
     '''the views a group of g utterances cuts out of the grow-only scratch 'stoi' of this (device, stream): a dict by
     the names of stoi_parts; cached per shape'''
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
-           torch.cuda.current_stream().cuda_stream, g, C, Ls, U, D)
-    hit = _stoi_ws.get(key)
-    if hit is not None and _lib._ws.get(key[:2] + ('stoi',)) is hit[0]:
-        return hit[1]
-    nbytes = stoi_workspace_bytes(g, C, Ls, U, D)
-    buf = _lib.workspace(nbytes, dev, 'stoi')
-    views, off = {}, 0
-    for name, shape, dtype in stoi_parts(g, C, Ls, U, D):
-        n = int(np.prod(shape)) * (8 if dtype == torch.float64 else 4)
-        views[name] = buf[off:off + n].view(dtype).view(shape)
-        off += (n + 255) & ~255
-    assert off == nbytes, (off, nbytes)
-    if len(_stoi_ws) >= 64:
-        _stoi_ws.clear()
-    _stoi_ws[key] = (buf, views)
-    return views
+    return _scratch('stoi', _stoi_ws, (g, C, Ls, U, D), lambda: stoi_parts(g, C, Ls, U, D),
+                    lambda: stoi_workspace_bytes(g, C, Ls, U, D), dev)[1]
 
 
 def stoi_resample(wav, smprate=None, out=None):
     '''float32 waveforms [B, 2C, Ls] (references first) -> the 10 kHz rows float32 [B, 2C + 1, L10], the last one the
     mixture of the references, ONE launch (danet_stoi_resample); out: optional tensor to write into'''
-    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.shape[1] % 2 == 0 \
-        and wav.stride(2) == 1 and wav.stride(1) == wav.shape[2] and wav.stride(0) == wav.shape[1] * wav.shape[2], \
-        (wav.dtype, wav.shape, wav.stride())
-    B, R, Ls = wav.shape
+    B, R, Ls = _chk('wav', wav, torch.float32, dim=3, contiguous=False).shape
+    # the strides themselves, not is_contiguous(), which lets any stride pass on a dimension of one element
+    assert R % 2 == 0 and wav.stride() == (R * Ls, Ls, 1), (wav.shape, wav.stride())
     t = stoi_tables(_stoi_smprate(smprate), wav.device)
-    sig = _bss_out(out, (B, R + 1, stoi_lengths(Ls, t['U'], t['D'])[0]), torch.float32, wav.device)
+    sig = _out('out', out, (B, R + 1, stoi_lengths(Ls, t['U'], t['D'])[0]), torch.float32, wav.device)
     with _lib.timed('stoi_resample'):
         _lib.stoi_check(_lib.load_stoi().danet_stoi_resample(_lib.stream(), B, R // 2, Ls, t['U'], t['D'], ptr(wav),
                                                              ptr(t['h']), ptr(sig)))
     return sig
 
 
+def _stoi_sig(sig):
+    '''the 10 kHz rows float32 [B, 2C + 1, L10], checked -> (B, C, L10, n = max(nf, 1), device)'''
+    B, R, L10 = _chk('sig', sig, torch.float32, dim=3).shape
+    assert R % 2, R
+    return B, R // 2, L10, max((L10 - 256) // 128 + 1 if L10 >= 256 else 0, 1), sig.device
+
+
 def stoi_frames(sig, smprate=None, out=None):
     '''the 10 kHz rows [B, 2C + 1, L10] -> (E [B, C, n], mask [B, C, n], kidx [B, C, n], M [B, C], Emax [B, C]) of
     the C references, n = max(nf, 1), ONE launch (danet_stoi_frames); out: optional tuple of the five'''
-    assert sig.is_cuda and sig.dtype == torch.float32 and sig.dim() == 3 and sig.is_contiguous() and sig.shape[1] % 2
-    B, R, L10 = sig.shape
-    C, dev = R // 2, sig.device
-    n = max((L10 - 256) // 128 + 1 if L10 >= 256 else 0, 1)
+    B, C, L10, n, dev = _stoi_sig(sig)
     out = out or (None,) * 5
-    E = _bss_out(out[0], (B, C, n), torch.float64, dev)
-    mask = _bss_out(out[1], (B, C, n), torch.int32, dev)
-    kidx = _bss_out(out[2], (B, C, n), torch.int32, dev)
-    M = _bss_out(out[3], (B, C), torch.int32, dev)
-    Emax = _bss_out(out[4], (B, C), torch.float64, dev)
+    E = _out('E', out[0], (B, C, n), torch.float64, dev)
+    mask = _out('mask', out[1], (B, C, n), torch.int32, dev)
+    kidx = _out('kidx', out[2], (B, C, n), torch.int32, dev)
+    M = _out('M', out[3], (B, C), torch.int32, dev)
+    Emax = _out('Emax', out[4], (B, C), torch.float64, dev)
     t = stoi_tables(_stoi_smprate(smprate), dev)
     with _lib.timed('stoi_frames'):
         _lib.stoi_check(_lib.load_stoi().danet_stoi_frames(_lib.stream(), B, C, L10, ptr(sig), ptr(t['w']), ptr(E),
@@ -1540,14 +1553,10 @@ def stoi_frames(sig, smprate=None, out=None):
 def stoi_bands(sig, kidx, M, smprate=None, out=None):
     '''the 10 kHz rows, k(.) and M of the references -> the band magnitudes T float64 [B, C, C + 2, 15, n] of the
     compacted frames of every (reference, paired signal), ONE launch (danet_stoi_bands; none when L10 < 256)'''
-    assert sig.is_cuda and sig.dtype == torch.float32 and sig.dim() == 3 and sig.is_contiguous() and sig.shape[1] % 2
-    B, R, L10 = sig.shape
-    C, dev = R // 2, sig.device
-    n = max((L10 - 256) // 128 + 1 if L10 >= 256 else 0, 1)
-    for t_, shape in ((kidx, (B, C, n)), (M, (B, C))):
-        assert t_.is_cuda and t_.device == dev and t_.dtype == torch.int32 and t_.is_contiguous() \
-            and tuple(t_.shape) == shape, (t_.dtype, t_.shape, shape)
-    T = _bss_out(out, (B, C, C + 2, 15, n), torch.float64, dev)
+    B, C, L10, n, dev = _stoi_sig(sig)
+    _chk('kidx', kidx, torch.int32, (B, C, n), dev=dev)
+    _chk('M', M, torch.int32, (B, C), dev=dev)
+    T = _out('out', out, (B, C, C + 2, 15, n), torch.float64, dev)
     t = stoi_tables(_stoi_smprate(smprate), dev)
     with _lib.timed('stoi_bands'):
         _lib.stoi_check(_lib.load_stoi().danet_stoi_bands(_lib.stream(), B, C, L10, ptr(sig), ptr(t['w']), ptr(t['tw']),
@@ -1558,11 +1567,10 @@ def stoi_bands(sig, kidx, M, smprate=None, out=None):
 def stoi_segments(T, M, nf, out=None):
     '''T [B, C, C + 2, 15, max(nf, 1)] and M [B, C] -> d float64 [B, C, C + 1, 2]: (STOI, ESTOI) of every reference
     against every estimate and the mixture, ONE launch (danet_stoi_segments)'''
-    assert T.is_cuda and T.dtype == torch.float64 and T.dim() == 5 and T.is_contiguous()
-    B, C, dev = T.shape[0], T.shape[1], T.device
+    B, C, dev = _chk('T', T, torch.float64, dim=5).shape[0], T.shape[1], T.device
     assert tuple(T.shape) == (B, C, C + 2, 15, max(int(nf), 1)), (T.shape, nf)
-    assert M.device == dev and M.dtype == torch.int32 and M.is_contiguous() and tuple(M.shape) == (B, C)
-    d = _bss_out(out, (B, C, C + 1, 2), torch.float64, dev)
+    _chk('M', M, torch.int32, (B, C), dev=dev)
+    d = _out('out', out, (B, C, C + 1, 2), torch.float64, dev)
     with _lib.timed('stoi_segments'):
         _lib.stoi_check(_lib.load_stoi().danet_stoi_segments(_lib.stream(), B, C, int(nf), ptr(T), ptr(M), ptr(d)))
     return d
@@ -1574,21 +1582,12 @@ def stoi_finalize(d, M, Emax, nf, b0=0, out=None):
     all rows when b0 + B = B_all.  out: optional (per_utt, perm_idx, flags, mean4, count) of a batch of B_all
     utterances to write into (default B_all = B)'''
     B, C, dev = d.shape[0], d.shape[1], d.device
-    for t_, shape, dtype in ((d, (B, C, C + 1, 2), torch.float64), (M, (B, C), torch.int32),
-                             (Emax, (B, C), torch.float64)):
-        assert t_.is_cuda and t_.device == dev and t_.dtype == dtype and t_.is_contiguous() \
-            and tuple(t_.shape) == shape, (t_.dtype, t_.shape, shape)
-    if out is None:
-        out = (torch.empty(B, 4, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.float64, device=dev),
-               torch.empty(1, dtype=torch.int32, device=dev))
-    per_utt, perm_idx, flags, mean4, count = out
-    B_all = per_utt.shape[0]
-    assert per_utt.dtype == torch.float64 and per_utt.is_contiguous() and tuple(per_utt.shape) == (B_all, 4)
-    assert perm_idx.dtype == torch.int32 and perm_idx.is_contiguous() and tuple(perm_idx.shape) == (B_all,)
-    assert flags.dtype == torch.int32 and flags.is_contiguous() and tuple(flags.shape) == (B_all,)
-    assert mean4.dtype == torch.float64 and mean4.is_contiguous() and mean4.numel() == 4
-    assert count.dtype == torch.int32 and count.numel() == 1
+    _chk('d', d, torch.float64, (B, C, C + 1, 2), dev=dev)
+    _chk('M', M, torch.int32, (B, C), dev=dev)
+    _chk('Emax', Emax, torch.float64, (B, C), dev=dev)
+    per_utt, perm_idx, flags, mean4, count = _result(B, 4, dev, flags=True, count=True) if out is None else out
+    B_all = _check_result(per_utt, perm_idx, flags, mean4, 4)
+    _chk('count', count, torch.int32, numel=1, contiguous=False, cuda=False)
     with _lib.timed('stoi_finalize'):
         _lib.stoi_check(_lib.load_stoi().danet_stoi_finalize(
             _lib.stream(), B, C, int(nf), ptr(d), ptr(M), ptr(Emax), int(b0), B_all, ptr(per_utt), ptr(perm_idx),
@@ -1599,10 +1598,7 @@ def stoi_finalize(d, M, Emax, nf, b0=0, out=None):
 def stoi_group(B, C, Ls, U, D):
     '''the utterances ops.stoi_eval takes at a time: the most whose scratch stays under STOI_SCRATCH_BYTES (one at
     least)'''
-    g = max(1, min(int(B), STOI_SCRATCH_BYTES // stoi_workspace_bytes(1, C, Ls, U, D)))
-    while g > 1 and stoi_workspace_bytes(g, C, Ls, U, D) > STOI_SCRATCH_BYTES:
-        g -= 1
-    return g
+    return _group(B, STOI_SCRATCH_BYTES, lambda g: stoi_workspace_bytes(g, C, Ls, U, D))
 
 
 def stoi_eval(src, est, fft_stride=None, wav=None, smprate=None, group=None, with_count=False):
@@ -1618,15 +1614,13 @@ def stoi_eval(src, est, fft_stride=None, wav=None, smprate=None, group=None, wit
     dev = src.device
     if wav is None:
         wav = synth_wav(src, est, fft_stride)
-    assert wav.is_cuda and wav.dtype == torch.float32 and wav.is_contiguous() and tuple(wav.shape[:2]) == (B, 2 * C)
+    assert tuple(_chk('wav', wav, torch.float32).shape[:2]) == (B, 2 * C), wav.shape
     smprate = _stoi_smprate(smprate)
     t = stoi_tables(smprate, dev)
     U, D, Ls = t['U'], t['D'], wav.shape[2]
     nf = stoi_lengths(Ls, U, D)[1]
     g = stoi_group(B, C, Ls, U, D) if group is None else max(1, min(int(group), B))
-    out = (torch.empty(B, 4, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-           torch.empty(B, dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.float64, device=dev),
-           torch.empty(1, dtype=torch.int32, device=dev))
+    out = _result(B, 4, dev, flags=True, count=True)
     for b0 in range(0, B, g):
         nb = min(g, B - b0)
         w = _stoi_workspace(nb, C, Ls, U, D, dev)
@@ -1652,22 +1646,17 @@ def neval_synth(src, est, noise, gain, fft_stride, window=None, out=None):
     '''references and UNPERMUTED estimates, complex64 [B, C, T, F], noise complex64 [B, T, F], gain float32 [B] or
     None (= 1) -> float32 waveforms [B, 2C + 1, (T - 1) * S]: references, estimates, then the synthesis of
     fl(gain * noise), ONE launch (danet_neval_synth).  window: float32 device vector [N] (default hparams.FFT_WND).'''
-    assert src.is_cuda and src.dtype == torch.complex64 and src.dim() == 4, (src.dtype, src.shape)
-    assert est.is_cuda and est.dtype == torch.complex64 and est.shape == src.shape and est.device == src.device
+    _chk('src', src, torch.complex64, dim=4, contiguous=False)
+    _chk('est', est, torch.complex64, src.shape, dev=src.device, contiguous=False)
     B, C, T, F = src.shape
-    assert noise.dtype == torch.complex64 and noise.device == src.device and tuple(noise.shape) == (B, T, F), \
-        (noise.device, noise.dtype, noise.shape)
-    if gain is not None:
-        assert gain.dtype == torch.float32 and gain.device == src.device and tuple(gain.shape) == (B,) \
-            and gain.is_contiguous(), (gain.device, gain.dtype, gain.shape)
+    _chk('noise', noise, torch.complex64, (B, T, F), dev=src.device, contiguous=False)
+    _chk('gain', gain, torch.float32, (B,), dev=src.device, optional=True)
     src, est, noise = src.contiguous(), est.contiguous(), noise.contiguous()
     N = 2 * (F - 1)
     window = _metric_window(src.device) if window is None else _f32(window).contiguous()
-    assert window.numel() == N and window.device == src.device, (window.numel(), N)
-    if out is None:
-        out = torch.empty(B, 2 * C + 1, max(T - 1, 0) * fft_stride, dtype=torch.float32, device=src.device)
-    assert out.dtype == torch.float32 and out.is_contiguous() \
-        and tuple(out.shape) == (B, 2 * C + 1, (T - 1) * fft_stride)
+    _chk('window', window, torch.float32, numel=N, dev=src.device)
+    assert T >= 1, T
+    out = _out('out', out, (B, 2 * C + 1, (T - 1) * fft_stride), torch.float32, src.device)
     with _lib.timed('neval_synth'):
         _lib.neval_check(_lib.load_neval().danet_neval_synth(
             _lib.stream(), B, C, T, N, fft_stride, ptr(torch.view_as_real(src)), ptr(torch.view_as_real(est)),
@@ -1694,17 +1683,13 @@ def si_sdr_noisy(src, est, noise, gain=None, fft_stride=None):
     sources to the noise -> (si_sdr, si_sdri, nsnr, per_utt [B, 3], perm_idx [B]): float64 / int32 device tensors
     of the caller's own (allocated here; the waveforms and Gram matrices live in a scratch cached per shape).  Three
     launches and nothing else on the device, no host synchronisation.'''
-    from .hparams import hparams
-    S = int(hparams.FFT_STRIDE if fft_stride is None else fft_stride)
+    S = _stride(fft_stride)
     B, C, T, F = src.shape
-    dev = src.device
-    ws = _wave_workspace('neval', _neval_ws, 2 * C + 1, 3, B, C, T, 2 * (F - 1), S, dev)
+    ws = _wave_workspace('neval', _neval_ws, 2 * C + 1, 3, B, C, T, 2 * (F - 1), S, src.device)
     wav, G = ws[1], ws[2]
     neval_synth(src, est, noise, gain, S, out=wav)
     neval_gram(wav, out=G)
-    mean3, per_utt, perm_idx = neval_finalize(G, out=(torch.empty(B, 3, dtype=torch.float64, device=dev),
-                                                      torch.empty(B, dtype=torch.int32, device=dev),
-                                                      torch.empty(3, dtype=torch.float64, device=dev)))
+    mean3, per_utt, perm_idx = neval_finalize(G, out=_result(B, 3, src.device))
     return mean3[0], mean3[1], mean3[2], per_utt, perm_idx
 
 
@@ -1724,9 +1709,8 @@ def wavloss_fwd(G, out=None):
     '''float64 Gram matrices [B, 2C, 2C] -> (loss_f64 [1], loss_f32 [1], per_utt [B], perm_idx int32 [B],
     pair int32 [B, C], coef float64 [B, C, 2]), ONE launch (danet_wavloss_fwd); out: optional tuple of the six to
     write into'''
-    assert G.is_cuda and G.dtype == torch.float64 and G.dim() == 3 and G.is_contiguous() and G.shape[1] == G.shape[2]
-    B, M = G.shape[0], G.shape[1]
-    assert M % 2 == 0, M
+    B, M = _chk('G', G, torch.float64, dim=3).shape[:2]
+    assert M == G.shape[2] and M % 2 == 0, G.shape
     C, dev = M // 2, G.device
     if out is None:
         out = (torch.empty(1, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.float32, device=dev),
@@ -1745,24 +1729,17 @@ def wavloss_bwd(wav, pair, coef, fft_size, fft_stride, window=None, dloss=None, 
     (ops.wavloss_fwd) -> complex64 dX [B, C, T, F], or with phasor float32 [B, T, F, 2] the real float32
     dsep [B, C, T, F].  dloss: float32 device scalar or None (= 1); window: float32 device vector [N] (default
     hparams.FFT_WND, uploaded once).'''
-    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 3 and wav.is_contiguous()
-    B, M, Ls = wav.shape
+    B, M, Ls = _chk('wav', wav, torch.float32, dim=3).shape
     N, S = int(fft_size), int(fft_stride)
     assert M % 2 == 0 and S >= 1 and Ls % S == 0, (M, Ls, S)
     C, T, F, dev = M // 2, Ls // S + 1, N // 2 + 1, wav.device
-    assert pair.dtype == torch.int32 and pair.is_contiguous() and tuple(pair.shape) == (B, C) and pair.device == dev
-    assert coef.dtype == torch.float64 and coef.is_contiguous() and tuple(coef.shape) == (B, C, 2) and coef.device == dev
+    _chk('pair', pair, torch.int32, (B, C), dev=dev)
+    _chk('coef', coef, torch.float64, (B, C, 2), dev=dev)
     window = _metric_window(dev) if window is None else _f32(window).contiguous()
-    assert window.numel() == N and window.device == dev, (window.numel(), N)
-    if dloss is not None:
-        assert dloss.dtype == torch.float32 and dloss.numel() == 1 and dloss.device == dev
-    if phasor is not None:
-        assert phasor.dtype == torch.float32 and phasor.is_contiguous() and tuple(phasor.shape) == (B, T, F, 2) \
-            and phasor.device == dev, (phasor.dtype, phasor.shape)
-    if out is None:
-        out = torch.empty(B, C, T, F, dtype=torch.complex64 if phasor is None else torch.float32, device=dev)
-    assert out.is_contiguous() and tuple(out.shape) == (B, C, T, F) and out.device == dev
-    assert out.dtype == (torch.complex64 if phasor is None else torch.float32), out.dtype
+    _chk('window', window, torch.float32, numel=N, dev=dev)
+    _chk('dloss', dloss, torch.float32, numel=1, dev=dev, contiguous=False, optional=True)
+    _chk('phasor', phasor, torch.float32, (B, T, F, 2), dev=dev, optional=True)
+    out = _out('out', out, (B, C, T, F), torch.complex64 if phasor is None else torch.float32, dev)
     with _lib.timed('wavloss_bwd'):
         _lib.wavloss_check(_lib.load_wavloss().danet_wavloss_bwd(
             _lib.stream(), B, C, T, N, S, ptr(wav), ptr(pair), ptr(coef), ptr(window), ptr(dloss), ptr(phasor),
@@ -1825,11 +1802,9 @@ def dpcl_workspace_bytes(B, N, E, C):
 
 
 def _dpcl_shapes(embed, src_pwr):
-    assert embed.is_cuda and embed.dtype == torch.float32 and embed.dim() == 3 and embed.is_contiguous(), \
-        (embed.device, embed.dtype, embed.shape)
-    B, N, E = embed.shape
-    assert src_pwr.dtype == torch.float32 and src_pwr.device == embed.device and src_pwr.dim() == 3 \
-        and src_pwr.is_contiguous() and src_pwr.shape[0] == B and src_pwr.shape[2] == N, (src_pwr.dtype, src_pwr.shape)
+    B, N, E = _chk('embed', embed, torch.float32, dim=3).shape
+    _chk('src_pwr', src_pwr, torch.float32, dim=3, dev=embed.device)
+    assert src_pwr.shape[0] == B and src_pwr.shape[2] == N, (src_pwr.shape, embed.shape)
     return B, N, E, src_pwr.shape[1]
 
 
@@ -1839,7 +1814,7 @@ def dpcl_stats(embed, src_pwr, ws=None):
     B, N, E, C = _dpcl_shapes(embed, src_pwr)
     if ws is None:
         ws = torch.empty(dpcl_workspace_bytes(B, N, E, C), dtype=torch.uint8, device=embed.device)
-    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == embed.device
+    _chk('ws', ws, torch.uint8, dev=embed.device)
     with _lib.timed('dpcl_stats'):
         _lib.dpcl_check(_lib.load_dpcl().danet_dpcl_stats(_lib.stream(), B, N, E, C, ptr(embed), ptr(src_pwr), ptr(ws),
                                                           ws.numel()))
@@ -1850,17 +1825,15 @@ def dpcl_finalize(ws, B, N, E, C, alpha, main=None, out=None):
     '''the workspace of dpcl_stats -> (per_utt float64 [B], dpcl float32 [1], total float32 [1] = main + alpha * dpcl,
     tables float32 [B, E, E + C], cs float32 [B, C + 1]), ONE launch (danet_dpcl_finalize).  main: float32 device
     scalar or None (= 0); alpha: a host number; out: optional tuple of the five to write into'''
-    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()
-    dev = ws.device
-    if main is not None:
-        assert main.dtype == torch.float32 and main.numel() == 1 and main.device == dev, (main.dtype, main.shape)
+    dev = _chk('ws', ws, torch.uint8).device
+    _chk('main', main, torch.float32, numel=1, dev=dev, contiguous=False, optional=True)
     if out is None:
         out = (torch.empty(B, dtype=torch.float64, device=dev), torch.empty(1, device=dev), torch.empty(1, device=dev),
                torch.empty(B, E, E + C, device=dev), torch.empty(B, C + 1, device=dev))
     per_utt, dpcl, total, tables, cs = out
-    assert per_utt.dtype == torch.float64 and per_utt.numel() == B and per_utt.is_contiguous()
-    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in (dpcl, total, tables, cs))
-    assert dpcl.numel() == 1 and total.numel() == 1 and tables.numel() == B * E * (E + C) and cs.numel() == B * (C + 1)
+    _chk('per_utt', per_utt, torch.float64, numel=B, cuda=False)
+    for name, t, n in (('dpcl', dpcl, 1), ('total', total, 1), ('tables', tables, B * E * (E + C)), ('cs', cs, B * (C + 1))):
+        _chk(name, t, torch.float32, numel=n, dev=dev)
     with _lib.timed('dpcl_finalize'):
         _lib.dpcl_check(_lib.load_dpcl().danet_dpcl_finalize(
             _lib.stream(), B, N, E, C, ptr(ws), ws.numel(), ptr(main), float(alpha), ptr(per_utt), ptr(dpcl),
@@ -1874,14 +1847,10 @@ def dpcl_bwd(embed, src_pwr, tables, cs, scale, dloss=None, out=None):
     -> dembed float32 [B, N, E]'''
     B, N, E, C = _dpcl_shapes(embed, src_pwr)
     dev = embed.device
-    assert tables.dtype == torch.float32 and tables.is_contiguous() and tuple(tables.shape) == (B, E, E + C) \
-        and tables.device == dev, (tables.dtype, tables.shape)
-    assert cs.dtype == torch.float32 and cs.is_contiguous() and tuple(cs.shape) == (B, C + 1) and cs.device == dev
-    if dloss is not None:
-        assert dloss.dtype == torch.float32 and dloss.numel() == 1 and dloss.device == dev
-    if out is None:
-        out = torch.empty(B, N, E, device=dev)
-    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, N, E) and out.device == dev
+    _chk('tables', tables, torch.float32, (B, E, E + C), dev=dev)
+    _chk('cs', cs, torch.float32, (B, C + 1), dev=dev)
+    _chk('dloss', dloss, torch.float32, numel=1, dev=dev, contiguous=False, optional=True)
+    out = _out('out', out, (B, N, E), torch.float32, dev)
     with _lib.timed('dpcl_bwd'):
         _lib.dpcl_check(_lib.load_dpcl().danet_dpcl_bwd(_lib.stream(), B, N, E, C, ptr(embed), ptr(src_pwr),
                                                         ptr(tables), ptr(cs), ptr(dloss), float(scale), ptr(out)))
@@ -1935,7 +1904,7 @@ def dpcl_loss(s_embed_flat, s_src_pwr, main, alpha):
 # On the extension library libdanet_stitch_hip.so, mapped at the first call: a run with INFER_CHUNK_LEN null, and an
 # input of at most one chunk, never gets here.  Three launches: overlap affinities -> permutation chain -> merge.
 STITCH_MAX_C = 4                                     # DANET_STITCH_MAX_C
-_stitch_ws = {}          # (device index, stream, n, C, L, F, V) -> (scratch, partials, S, perm)
+_stitch_ws = {}          # (device index, stream, n, C, L, F, V, T) -> (scratch, views)
 _stitch_fades = {}       # (device index, V) -> float32 device vector [V]
 
 
@@ -1963,7 +1932,7 @@ def stitch_workspace_bytes(T, L, V, C, F):
 
 def stitch_fade(V, dev):
     '''w_k = (k + 1) / (V + 1), k < V: computed in float64, rounded once to float32, uploaded once per (device, V)'''
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(V))
+    key = (_dev_index(dev), int(V))
     t = _stitch_fades.get(key)
     if t is None:
         w = ((np.arange(V, dtype=np.float64) + 1.0) / (V + 1.0)).astype(np.float32)
@@ -1972,9 +1941,7 @@ def stitch_fade(V, dev):
 
 
 def _stitch_shapes(mags, T, V):
-    assert mags.is_cuda and mags.dtype == torch.float32 and mags.dim() == 4 and mags.is_contiguous(), \
-        (mags.device, mags.dtype, mags.shape)
-    n, C, L, F = mags.shape
+    n, C, L, F = _chk('mags', mags, torch.float32, dim=4).shape
     assert n == stitch_chunks(T, L, V), (n, T, L, V)
     return n, C, L, F
 
@@ -1985,7 +1952,7 @@ def stitch_affinity(mags, T, V, ws=None):
     n, C, L, F = _stitch_shapes(mags, T, V)
     if ws is None:
         ws = torch.empty(stitch_workspace_bytes(T, L, V, C, F), dtype=torch.uint8, device=mags.device)
-    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == mags.device
+    _chk('ws', ws, torch.uint8, dev=mags.device)
     with _lib.timed('stitch_affinity'):
         _lib.stitch_check(_lib.load_stitch().danet_stitch_affinity(_lib.stream(), T, L, V, C, F, ptr(mags), ptr(ws),
                                                                    ws.numel()))
@@ -1995,14 +1962,14 @@ def stitch_affinity(mags, T, V, ws=None):
 def stitch_assign(ws, T, L, V, C, F, out=None):
     '''the workspace of stitch_affinity -> (S float64 [n - 1, C, C], perm int32 [n, C]), ONE launch of one workgroup
     (danet_stitch_assign): perm[i][c] is the channel of chunk i that is output channel c.  out: optional (S, perm)'''
-    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()
+    _chk('ws', ws, torch.uint8)
     n = stitch_chunks(T, L, V)
     if out is None:
         out = (torch.empty(max(n - 1, 0), C, C, dtype=torch.float64, device=ws.device),
                torch.empty(n, C, dtype=torch.int32, device=ws.device))
     S, perm = out
-    assert S.dtype == torch.float64 and S.is_contiguous() and S.numel() == (n - 1) * C * C and S.device == ws.device
-    assert perm.dtype == torch.int32 and perm.is_contiguous() and perm.numel() == n * C and perm.device == ws.device
+    _chk('S', S, torch.float64, numel=(n - 1) * C * C, dev=ws.device)
+    _chk('perm', perm, torch.int32, numel=n * C, dev=ws.device)
     with _lib.timed('stitch_assign'):
         _lib.stitch_check(_lib.load_stitch().danet_stitch_assign(_lib.stream(), T, L, V, C, F, ptr(ws), ws.numel(),
                                                                  ptr(S), ptr(perm)))
@@ -2015,41 +1982,28 @@ def stitch_merge(mags, phasor, perm, T, V, fade=None, out=None):
     the mixture phasor, ONE launch (danet_stitch_merge).  fade: float32 device vector [V] (default stitch_fade)'''
     n, C, L, F = _stitch_shapes(mags, T, V)
     dev = mags.device
-    assert phasor.dtype == torch.float32 and phasor.is_contiguous() and tuple(phasor.shape) == (n, L, F, 2) \
-        and phasor.device == dev, (phasor.dtype, phasor.shape)
-    assert perm.dtype == torch.int32 and perm.is_contiguous() and tuple(perm.shape) == (n, C) and perm.device == dev
+    _chk('phasor', phasor, torch.float32, (n, L, F, 2), dev=dev)
+    _chk('perm', perm, torch.int32, (n, C), dev=dev)
     fade = stitch_fade(V, dev) if fade is None else fade
-    assert fade.dtype == torch.float32 and fade.is_contiguous() and fade.numel() == V and fade.device == dev
-    if out is None:
-        out = torch.empty(C, T, F, dtype=torch.complex64, device=dev)
-    assert out.dtype == torch.complex64 and out.is_contiguous() and tuple(out.shape) == (C, T, F) and out.device == dev
+    _chk('fade', fade, torch.float32, numel=V, dev=dev)
+    out = _out('out', out, (C, T, F), torch.complex64, dev)
     with _lib.timed('stitch_merge'):
         _lib.stitch_check(_lib.load_stitch().danet_stitch_merge(
             _lib.stream(), T, L, V, C, F, ptr(mags), ptr(phasor), ptr(fade), ptr(perm), ptr(torch.view_as_real(out))))
     return out
 
 
+def _stitch_parts(n, C, L, F, T, V):
+    '''[(name, shape, dtype)] of the scratch of ops.stitch: the library's workspace, then S and perm, its own'''
+    return [('partials', (stitch_workspace_bytes(T, L, V, C, F),), torch.uint8), ('S', (n - 1, C, C), torch.float64),
+            ('perm', (n, C), torch.int32)]
+
+
 def _stitch_workspace(n, C, L, F, T, V, dev):
     '''(buffer, partials, S, perm): the views one shape cuts out of the grow-only scratch 'stitch' of this (device,
     stream), each at a multiple of 256 bytes; cached per shape'''
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
-           torch.cuda.current_stream().cuda_stream, n, C, L, F, V, T)
-    hit = _stitch_ws.get(key)
-    if hit is not None and _lib._ws.get(key[:2] + ('stitch',)) is hit[0]:
-        return hit
-    sizes = (stitch_workspace_bytes(T, L, V, C, F), (n - 1) * C * C * 8, n * C * 4)
-    offs, off = [], 0
-    for size in sizes:
-        offs.append(off)
-        off += (size + 255) & ~255
-    buf = _lib.workspace(off, dev, 'stitch')
-    part = buf[offs[0]:offs[0] + sizes[0]]
-    S = buf[offs[1]:offs[1] + sizes[1]].view(torch.float64).view(n - 1, C, C)
-    perm = buf[offs[2]:offs[2] + sizes[2]].view(torch.int32).view(n, C)
-    if len(_stitch_ws) >= 64:
-        _stitch_ws.clear()
-    hit = _stitch_ws[key] = (buf, part, S, perm)
-    return hit
+    buf, v = _scratch('stitch', _stitch_ws, (n, C, L, F, V, T), lambda: _stitch_parts(n, C, L, F, T, V), None, dev)
+    return buf, v['partials'], v['S'], v['perm']
 
 
 def stitch(mags, phasor, T, V):
