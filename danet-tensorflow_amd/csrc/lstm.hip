@@ -129,7 +129,7 @@ __device__ __forceinline__ bool spin_fail(unsigned& spins, int* status, int lane
     ((unsigned long long*)((char*)a.status_ws + 64))[(size_t)s * 8 + (slot)] = wall_clock64(); } while (0)
 #define TRACE_AT_VAL(thr, slot, v) do { if (blockIdx.x == 0 && threadIdx.x == (thr)) \
     ((unsigned long long*)((char*)a.status_ws + 64))[(size_t)s * 8 + (slot)] = (v); } while (0)
-#define TRACE_BYTES(T) ((size_t)(T) * 64)
+#define TRACE_BYTES(T) ((size_t)((T) + 1) * 64)   // record T: the fused forward's prologue (start, loop entry)
 #else
 #define TRACE_AT(thr, slot) do {} while (0)
 #define TRACE_AT_VAL(thr, slot, v) do {} while (0)
@@ -587,10 +587,30 @@ struct LstmFwdFxArgs {
 // (Splitting at the PRODUCER instead, with
 // the pieces as the exchange payload, was built first and lost 0.7 us per step to the hand-off:
 // profiles/r05_b_fwd_producer_split.txt.)
+//
+// The launch's prologue, switched by -DFX_STEP_PATH for A/B builds (profiles/fwd_fx_step_path.md; 0 is the kernel as
+// it was before):
+//   1  FETCH: the recurrent weight fragments come straight from global memory, like the input half's: per-lane
+//      loads, all of a launch's stationary loads (wreg, wx, wxe, bias, x of step 0) issued before the first
+//      split_pair.  Before, the workgroup staged its KP x 32 weights through LDS: KP / 8 rounds of one 4-byte
+//      gather load and one LDS store per thread, a barrier, and LDS reads into the same registers -- 18 us of a
+//      launch at D = 600, 15 us at D = 132, against 7.5 and 4.4 us now.
+// (Two more parts were built and measured with it and are gone again, same document: 2 ONEBAR, a double-buffered
+// `red` without the step's closing barrier, +4.2 % on the train step -- that barrier is what keeps waves 2 and 3
+// from issuing their exchange loads before the owners have published; 4 HALFBLK, the half-empty last recurrent
+// k-block split without its zero half, +0.3 %.)
+#ifndef FX_STEP_PATH
+#define FX_STEP_PATH 1
+#endif
+// LDS of a launch: recurrent weights [KP/4][32][4] (not with FETCH) | red [NW][16][33]
+static size_t fwd_fx_lds_bytes(int KP) {
+  return (((FX_STEP_PATH & 1) ? 0 : (size_t)KP * 32) + (size_t)4 * 16 * 33) * sizeof(float);
+}
 template <int CHX, int CHE>
 __global__ __launch_bounds__(256) void lstm_fwd_fx_kernel(LstmFwdFxArgs a) {
   constexpr int NW = 4, CH = FWD_CH;
   constexpr int NB = (CH + 1) / 2;      // k-blocks of 32 = pairs of 16-k groups per wave
+  constexpr bool FETCH = (FX_STEP_PATH & 1) != 0;
   constexpr int XBA = 1;   // k-blocks of the input half done before the exchange loads are issued (0: retries)
   // ... and k-groups of it where it stays on the fp32 instructions (the bottom layer): ALL of them.
   // With the gate phase at 45 vector instructions (hardware reciprocal, walking pointers) the next
@@ -600,9 +620,12 @@ __global__ __launch_bounds__(256) void lstm_fwd_fx_kernel(LstmFwdFxArgs a) {
   // none 305 (profiles/r05_k_fwd_load_point.txt).
   constexpr int XGA = CHX;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  // smem: recurrent weights [KP/4][32][4] (read once into registers) | red [NW][16][33]
+  // smem: recurrent weights [KP/4][32][4] (read once into registers; not with FETCH) | red [NW][16][33]
   float* Wl = smem;
-  float* red = smem + (size_t)a.KP * 32;
+  float* red = smem + (FETCH ? (size_t)0 : (size_t)a.KP * 32);
+#ifdef DANET_LSTM_TRACE
+  const unsigned long long trace_t0 = wall_clock64();    // prologue: launch's first instruction -> loop entry
+#endif
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool early = wave >= 2;      // uniform
@@ -617,7 +640,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_fx_kernel(LstmFwdFxArgs a) {
   const int b0 = grp * 16;
   const float* Wd = a.W[dir];
 
-  {
+  if constexpr (!FETCH) {
     const float* W = Wd + (size_t)D * a.ldw;     // recurrent rows
     for (int idx = tid; idx < a.KP * 32; idx += 64 * NW) {
       const int k = idx >> 5, n = idx & 31;
@@ -626,8 +649,8 @@ __global__ __launch_bounds__(256) void lstm_fwd_fx_kernel(LstmFwdFxArgs a) {
       if (k < H && u < H) v = W[(size_t)k * a.ldw + gate * H + u];
       Wl[((k >> 2) * 32 + n) * 4 + (k & 3)] = v;
     }
+    __syncthreads();
   }
-  __syncthreads();
 
   const unsigned ybytes = (unsigned)((size_t)(T + 2) * B * a.ldy * sizeof(float));
   const __amdgpu_buffer_rsrc_t yres = make_rsrc(a.ypad, ybytes);
@@ -651,7 +674,18 @@ __global__ __launch_bounds__(256) void lstm_fwd_fx_kernel(LstmFwdFxArgs a) {
   // B operand of v_mfma_f32_16x16x32_bf16: lane (n = lane % 16, kq = lane / 16) holds column n's
   // weights of the 8 k this lane GROUP's A fragments carry in k-block b: elements 0..3 = k-group 2b,
   // elements 4..7 = k-group 2b+1, k = 16 (g * NW + wave) + 4 kq + j each.
+  // FETCH: one weight of W[dir] or, where the fragment is padding, zero; the load itself is unconditional (a
+  // padding lane reads element 0), so that a launch's stationary loads are one run of loads in flight together
+  auto wval = [&](bool ok, size_t idx) -> float {
+    if constexpr (FETCH) {
+      const float v = Wd[ok ? idx : (size_t)0];
+      return ok ? v : 0.f;
+    } else {
+      return ok ? Wd[idx] : 0.f;
+    }
+  };
   uint32_t wreg[NB][3][2][4];
+  float wraw[FETCH ? NB : 1][2][8];       // FETCH: the fragments as loaded, split behind the last load
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -661,11 +695,19 @@ __global__ __launch_bounds__(256) void lstm_fwd_fx_kernel(LstmFwdFxArgs a) {
       for (int e = 0; e < 8; ++e) {
         const int g = 2 * b + (e >> 2);
         const int k = (g * NW + wave) * 16 + fq * 4 + (e & 3);
-        w[e] = (g < CH && k < a.KP) ? Wl[((k >> 2) * 32 + nt * 16 + fr) * 4 + (k & 3)] : 0.f;
+        if constexpr (FETCH) {
+          const int n = nt * 16 + fr;
+          const int gate = n >> 3, u = u0 + (n & 7);
+          wraw[b][nt][e] = wval(g < CH && k < H && u < H, (size_t)(D + k) * a.ldw + gate * H + u);
+        } else {
+          w[e] = (g < CH && k < a.KP) ? Wl[((k >> 2) * 32 + nt * 16 + fr) * 4 + (k & 3)] : 0.f;
+        }
       }
+      if constexpr (!FETCH) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        split_pair(w[2 * q], w[2 * q + 1], wreg[b][0][nt][q], wreg[b][1][nt][q], wreg[b][2][nt][q]);
+        for (int q = 0; q < 4; ++q)
+          split_pair(w[2 * q], w[2 * q + 1], wreg[b][0][nt][q], wreg[b][1][nt][q], wreg[b][2][nt][q]);
+      }
     }
   // input half: the same six-piece arithmetic, k-block b = window k-groups 2b | 2b+1 of this wave
   // (early list: early k-groups 2b | 2b+1; an odd last group is paired with zeros)
@@ -688,18 +730,37 @@ __global__ __launch_bounds__(256) void lstm_fwd_fx_kernel(LstmFwdFxArgs a) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) split_pair(w[2 * q], w[2 * q + 1], o[0][q], o[1][q], o[2][q]);
   };
+  // (FETCH: the same eight weights, loaded only)
+  auto wxload = [&](int kga, int kgb, bool on, int nt, float (&w)[8]) {
+    const int n = nt * 16 + fr;
+    const int gate = n >> 3, u = u0 + (n & 7);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int kg = (e < 4) ? kga : kgb;
+      const int k = kg * 16 + fq * 4 + (e & 3);
+      w[e] = wval(on && kg >= 0 && u < H && k < D, (size_t)k * a.ldw + gate * H + u);
+    }
+  };
   uint32_t wx[XBW][2][3][4];
+  float wxraw[FETCH ? XBW : 1][2][8];
 #pragma unroll
   for (int b = 0; b < (XBF ? XBW : 0); ++b)
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) wxfrag((2 * b) * NW + wave, (2 * b + 1) * NW + wave, true, nt, wx[b][nt]);
+    for (int nt = 0; nt < 2; ++nt) {
+      if constexpr (FETCH) wxload((2 * b) * NW + wave, (2 * b + 1) * NW + wave, true, nt, wxraw[FETCH ? b : 0][nt]);
+      else wxfrag((2 * b) * NW + wave, (2 * b + 1) * NW + wave, true, nt, wx[b][nt]);
+    }
   uint32_t wxe[XBE][2][3][4];
+  float wxeraw[FETCH ? XBE : 1][2][8];
 #pragma unroll
   for (int b = 0; b < (XBF ? XBE : 0); ++b)
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-      wxfrag(NW * CHX + 2 * (2 * b) + (wave - 2), (2 * b + 1 < CHE) ? NW * CHX + 2 * (2 * b + 1) + (wave - 2) : -1,
-             early, nt, wxe[b][nt]);
+    for (int nt = 0; nt < 2; ++nt) {
+      const int kga = NW * CHX + 2 * (2 * b) + (wave - 2);
+      const int kgb = (2 * b + 1 < CHE) ? NW * CHX + 2 * (2 * b + 1) + (wave - 2) : -1;
+      if constexpr (FETCH) wxload(kga, kgb, early, nt, wxeraw[FETCH ? b : 0][nt]);
+      else wxfrag(kga, kgb, early, nt, wxe[b][nt]);
+    }
 
   // (fp32 fragments for the narrow input of the bottom layer, see XBF)
   f32x4 wxf[XBF ? 1 : CHX][2];
@@ -784,6 +845,31 @@ __global__ __launch_bounds__(256) void lstm_fwd_fx_kernel(LstmFwdFxArgs a) {
     for (int g = 0; g < CHE; ++g)
       xce[g] = __builtin_amdgcn_raw_buffer_load_b128(
           xres, xoffe[g] == 0xFFFFFFFFu ? xbytes : xoffe[g] + (unsigned)t0 * xblk, 0, 0);
+    if constexpr (FETCH) {
+      // every stationary load of the launch is issued: split the weight fragments as they arrive
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            split_pair(wraw[b][nt][2 * q], wraw[b][nt][2 * q + 1], wreg[b][0][nt][q], wreg[b][1][nt][q], wreg[b][2][nt][q]);
+#pragma unroll
+      for (int b = 0; b < (XBF ? XBW : 0); ++b)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            split_pair(wxraw[b][nt][2 * q], wxraw[b][nt][2 * q + 1], wx[b][nt][0][q], wx[b][nt][1][q], wx[b][nt][2][q]);
+#pragma unroll
+      for (int b = 0; b < (XBF ? XBE : 0); ++b)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            split_pair(wxeraw[b][nt][2 * q], wxeraw[b][nt][2 * q + 1], wxe[b][nt][0][q], wxe[b][nt][1][q], wxe[b][nt][2][q]);
+    }
     // wait for them HERE: loads still pending at loop entry make the compiler put one
     // s_waitcnt vmcnt(0) into the loop header, where it then also waits for the previous
     // step's publish stores on every iteration
@@ -847,6 +933,13 @@ __global__ __launch_bounds__(256) void lstm_fwd_fx_kernel(LstmFwdFxArgs a) {
     }
   }
 
+#ifdef DANET_LSTM_TRACE
+  if (blockIdx.x == 0 && threadIdx.x == 0) {     // record T of the trace: the prologue's two stamps
+    unsigned long long* tr = (unsigned long long*)((char*)a.status_ws + 64) + (size_t)T * 8;
+    tr[0] = trace_t0;
+    tr[1] = wall_clock64();
+  }
+#endif
   for (int s = 0; s < T; ++s) {
     const int t = dir ? (T - 1 - s) : s;
     const int blk_prev = dir ? (t + 2) : t;
@@ -1995,7 +2088,7 @@ extern "C" int danet_lstm_fwd_fused(danet_stream_t stream_, int T, int B, int H,
   a.P = cdiv(H, LSTM_UNITS_FWD); a.G = cdiv(B, 16); a.KP = cdiv(H, 16) * 16;
   a.DP = cdiv(D, 16) * 16;
   a.xmap = (danet_opt(OPT_LSTM_XMAP) >= 0 ? danet_opt(OPT_LSTM_XMAP) : 1);
-  const size_t lds = ((size_t)a.KP * 32 + (size_t)4 * 16 * 33) * sizeof(float);
+  const size_t lds = fwd_fx_lds_bytes(a.KP);
   const size_t blk = (size_t)B * ldy * sizeof(float);
   if (!(flags & DANET_LSTM_PREFILLED)) {
     FillList fl;

@@ -2,7 +2,8 @@
 '''Per-step phase timeline of the persistent LSTM kernels (diagnostic).
 
 Build the trace variant first:   python danet-tensorflow_amd/_build.py --trace
-Run on a GPU box:                python tools/trace_lstm.py [B T H]
+Run on a GPU box:                python tools/trace_lstm.py [B T H] [--fused-only]
+(DANET_LIB_PATH names another trace build, e.g. one of _build.py --variant NAME -DDANET_LSTM_TRACE -DFX_STEP_PATH=n)
 
 Workgroup 0 / wave 0 stamps each step with the 100 MHz wall clock:
   A top of step | B exchange valid (retries in G) | C MFMAs done | D barrier 1 |
@@ -21,7 +22,8 @@ import __graft_entry__ as g  # noqa: E402
 g.load_package()
 from danet_amd import _lib  # noqa: E402
 
-_lib.LIB_PATH = os.path.join(ROOT, 'danet-tensorflow_amd', 'csrc', 'libdanet_hip_trace.so')
+_lib.LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(ROOT, 'danet-tensorflow_amd', 'csrc',
+                                                                 'libdanet_hip_trace.so')
 L = _lib.load()
 ptr = _lib.ptr
 
@@ -43,10 +45,12 @@ def report(name, ws, T):
 def report_fused(name, ws, T):
     '''lstm_fwd_fx_kernel: 0 top | 1 first quarter of the input half + loads issued | 2 rest
     of the input half issued | 3 exchange valid (6 retries) | 4 recurrent MFMAs + reduce barrier
-    | 5 gate math, publish | 7 barrier'''
-    tr = ws[64:64 + T * 64].view(torch.int64).view(T, 8).cpu().numpy().astype(np.float64)
-    tr = tr[2:]
+    | 5 gate math, publish | 7 barrier; record T: the launch's first instruction | loop entry (the prologue)'''
+    tr = ws[64:64 + (T + 1) * 64].view(torch.int64).view(T + 1, 8).cpu().numpy().astype(np.float64)
     us = lambda a: a / 100.0
+    print('%s: prologue %.2f us, loop %.2f us (workgroup 0, this launch)' % (
+        name, us(tr[T, 1] - tr[T, 0]), us(tr[T - 1, 7] - tr[T, 1])))
+    tr = tr[2:T]
     step = us(np.diff(tr[:, 0]))
     ph = dict(top_to_loads=us(tr[:, 1] - tr[:, 0]), input_half_rest=us(tr[:, 2] - tr[:, 1]),
               rest_to_valid=us(tr[:, 3] - tr[:, 2]), recurrent_reduce=us(tr[:, 4] - tr[:, 3]),
@@ -83,10 +87,13 @@ def fused(B, T, H, D):
 
 
 def main():
-    B, T, H = (int(x) for x in sys.argv[1:4]) if len(sys.argv) >= 4 else (32, 128, 300)
-    if _lib.get_option('lstm_fwd_fused') == 1:
+    argv = [x for x in sys.argv[1:] if x != '--fused-only']
+    B, T, H = (int(x) for x in argv[:3]) if len(argv) >= 3 else (32, 128, 300)
+    if _lib.get_option('lstm_fwd_fused') == 1 or '--fused-only' in sys.argv:
         fused(B, T, H, 2 * H)
         fused(B, T, H, 132)
+    if '--fused-only' in sys.argv:
+        return
     dev = torch.device('cuda')
     st = torch.cuda.current_stream().cuda_stream
     ndir = 2
