@@ -1,5 +1,5 @@
 '''
-Builds the twenty HIP libraries (gfx950 only) in-tree with hipcc.
+Builds the twenty-one HIP libraries (gfx950 only) in-tree with hipcc.
 
     python danet-tensorflow_amd/_build.py [--force]
 
@@ -26,6 +26,7 @@ Builds the twenty HIP libraries (gfx950 only) in-tree with hipcc.
     libdanet_phase_hip.so         csrc/phase/*.hip         include/danet_phase_hip.h, csrc/{ext_core,wave_metric}.h
     libdanet_online_hip.so        csrc/online/*.hip        include/danet_online_hip.h, csrc/ext_core.h
     libdanet_causal_hip.so        csrc/causal/*.hip        include/danet_causal_hip.h, csrc/ext_core.h
+    libdanet_tonline_hip.so       csrc/tonline/*.hip       include/danet_tonline_hip.h, csrc/ext_core.h
 
 One object per source under <source directory>/build/, compiled in parallel and linked with the
 exports.map of the source directory; an object is rebuilt only when its source or one of its library's
@@ -96,7 +97,8 @@ STOI = _extension('stoi', *_shared('ext_core'))
 PHASE = _extension('phase', *_shared('ext_core', 'wave_metric'))
 ONLINE = _extension('online', *_shared('ext_core'))
 CAUSAL = _extension('causal', *_shared('ext_core'))
-MORE_EXTENSIONS = (STITCH, BSS, STOI, PHASE, ONLINE, CAUSAL)
+TONLINE = _extension('tonline', *_shared('ext_core'))
+MORE_EXTENSIONS = (STITCH, BSS, STOI, PHASE, ONLINE, CAUSAL, TONLINE)
 METRIC_LIB = METRIC.out
 NOISE_LIB = NOISE.out
 LEVEL_LIB = LEVEL.out
@@ -110,6 +112,7 @@ STOI_LIB = STOI.out
 PHASE_LIB = PHASE.out
 ONLINE_LIB = ONLINE.out
 CAUSAL_LIB = CAUSAL.out
+TONLINE_LIB = TONLINE.out
 
 
 def _sources(src_dir):
@@ -253,6 +256,10 @@ def build_online(force=False, verbose=True):
 
 def build_causal(force=False, verbose=True):
     return _build_spec(CAUSAL, force, verbose)
+
+
+def build_tonline(force=False, verbose=True):
+    return _build_spec(TONLINE, force, verbose)
 
 
 def build_variant(name, defs):

@@ -1,7 +1,7 @@
 '''
-ctypes binding of the twenty HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
+ctypes binding of the twenty-one HIP libraries (the C ABIs declared in include/danet*_hip.h): the core
 libdanet_hip.so and the conv, dropout, prep, mix, speed, reverb, metric, noise, level, wavloss, gclip, dpcl, neval,
-stitch, bss, stoi, phase, online and causal extension libraries.  Each is described
+stitch, bss, stoi, phase, online, causal and tonline extension libraries.  Each is described
 once, by a record of ALL_LIBRARIES, LATER_LIBRARIES, EXTENSIONS or MORE_EXTENSIONS; one loader (_load) and one error check (_check) serve them all.
 
 There is NO fallback: if a shared library is missing or a call fails, a
@@ -312,8 +312,20 @@ CAUSAL_PROTOTYPES = {
     'danet_causal_project': (c_int, [c_p, c_int, c_int, c_int, c_p, c_int, c_p, c_int, c_p, c_int]),
 }
 
+# name -> (restype, argtypes); mirrors include/danet_tonline_hip.h
+TONLINE_PROTOTYPES = {
+    'danet_tonline_abi_version': (c_int, []),
+    'danet_tonline_last_error': (ctypes.c_char_p, []),
+    'danet_tonline_frame_sums': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p]),
+    'danet_tonline_scan': (c_int, [c_p, c_int, c_int, c_int, c_int, c_f64, c_int, c_f64, c_p, c_p, c_p, c_p]),
+    'danet_tonline_scan_bwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_f64, c_int, c_p, c_p, c_p]),
+    'danet_tonline_sums_bwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
+    'danet_tonline_separate_bwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p,
+                                           c_p]),
+}
+
 # ---- the libraries -------------------------------------------------------------
-# Twenty shared objects, each with a header, an ABI version and a prototype table of its own (the core's
+# Twenty-one shared objects, each with a header, an ABI version and a prototype table of its own (the core's
 # table stays exactly the core header's).  A missing library is a hard error for every one of them.
 # To add one: a record here, its prototype table above, a source directory csrc/<name>/ with an
 # exports.map (and a record in _build.py), and a header include/danet_<name>_hip.h.  LIBRARIES stays the five
@@ -427,7 +439,14 @@ CAUSAL_ABI_VERSION = 1
 CAUSAL = Library('causal', 'libdanet_causal_hip.so', 'CAUSAL_LIB_PATH', '_causal', CAUSAL_PROTOTYPES,
                  CAUSAL_ABI_VERSION, 'danet_causal_', 'the lstm-causal encoder and streaming inference need the HIP '
                  'extension library')
-MORE_EXTENSIONS = (STITCH, BSS, STOI, PHASE, ONLINE, CAUSAL)
+# loaded at the first train step (or forward pass with the train branch) of a model built with TRAIN_ESTIMATOR_METHOD =
+# "truth-online" only (ops.TruthOnlineAttractorFn / ops.OnlineSeparateFn): a run with another train estimator, and
+# every valid_step, infer and stream session, never maps it
+TONLINE_ABI_VERSION = 1
+TONLINE = Library('tonline', 'libdanet_tonline_hip.so', 'TONLINE_LIB_PATH', '_tonline', TONLINE_PROTOTYPES,
+                  TONLINE_ABI_VERSION, 'danet_tonline_', 'TRAIN_ESTIMATOR_METHOD = "truth-online" needs the HIP '
+                  'extension library')
+MORE_EXTENSIONS = (STITCH, BSS, STOI, PHASE, ONLINE, CAUSAL, TONLINE)
 
 # DANET_LIB_PATH: an A/B build of the same sources (_build.build_variant), never a different backend
 LIB_PATH = os.environ.get('DANET_LIB_PATH') or os.path.join(_CSRC, CORE.so)
@@ -450,8 +469,9 @@ STOI_LIB_PATH = os.path.join(_CSRC, STOI.so)
 PHASE_LIB_PATH = os.path.join(_CSRC, PHASE.so)
 ONLINE_LIB_PATH = os.path.join(_CSRC, ONLINE.so)
 CAUSAL_LIB_PATH = os.path.join(_CSRC, CAUSAL.so)
+TONLINE_LIB_PATH = os.path.join(_CSRC, TONLINE.so)
 _lib = _conv = _dropout = _prep = _mix = _speed = _reverb = _metric = _noise = _level = _wavloss = _gclip = _dpcl = None
-_neval = _stitch = _bss = _stoi = _phase = _online = _causal = None
+_neval = _stitch = _bss = _stoi = _phase = _online = _causal = _tonline = None
 _lock = threading.Lock()
 
 
@@ -719,6 +739,17 @@ def load_causal():
 def causal_check(rc):
     if rc != 0:
         _check(CAUSAL, rc)
+
+
+def load_tonline():
+    if _tonline is not None:
+        return _tonline
+    return _load(TONLINE)
+
+
+def tonline_check(rc):
+    if rc != 0:
+        _check(TONLINE, rc)
 
 
 # ---- switches ------------------------------------------------------------------

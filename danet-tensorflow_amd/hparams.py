@@ -75,6 +75,11 @@ unchanged.  Differences, all deliberate:
   `Model.infer` feed the recording through such a session in blocks of that many frames; it needs that encoder and
   that estimator, `BATCH_SIZE` <= 16 when `infer` runs, and not `INFER_CHUNK_LEN` or `PHASE_REFINE_ITERS`;
   `train_step` and `valid_step` never look at it.
+* `TRAIN_ESTIMATOR_METHOD = "truth-online"` trains under the conditions `INFER_ESTIMATOR_METHOD = "online"` runs in:
+  frame t is separated with the running, forgetting-weighted means of the embedding under the ideal assignment of
+  the frames <= t (the first T0 frames share those of frame T0 - 1), with an exact backward
+  (include/danet_tonline_hip.h).  It needs `INFER_ESTIMATOR_METHOD = "online"`, whose `ONLINE_INIT_FRAMES` and
+  `ONLINE_MEMORY_FRAMES` it shares; no key of its own; not as `INFER_ESTIMATOR_METHOD` (it uses the truth).
 * `get_regularizer()` returns None: the reference attaches a regulariser that
   never reaches the loss (`main.py:228-229` vs `:289-290,358`).
 '''

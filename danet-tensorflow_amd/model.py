@@ -357,6 +357,10 @@ class Model(object):
         if hparams.TRAIN_ESTIMATOR_METHOD == 'online':
             raise ValueError('TRAIN_ESTIMATOR_METHOD cannot be "online": the online estimator has no backward, it is an '
                              'inference estimator (INFER_ESTIMATOR_METHOD)')
+        if hparams.TRAIN_ESTIMATOR_METHOD == 'truth-online' and hparams.INFER_ESTIMATOR_METHOD != 'online':
+            raise ValueError('TRAIN_ESTIMATOR_METHOD = "truth-online" needs INFER_ESTIMATOR_METHOD = "online" (got %r): it '
+                             'is the training twin of that estimator and takes its hold length and forgetting factor '
+                             '(ONLINE_INIT_FRAMES / ONLINE_MEMORY_FRAMES) from it' % (hparams.INFER_ESTIMATOR_METHOD,))
         if hparams.INFER_ESTIMATOR_METHOD != 'online':
             for key, v in (('ONLINE_INIT_FRAMES', t0), ('ONLINE_MEMORY_FRAMES', tau)):
                 if v is not None:
@@ -585,7 +589,9 @@ class Model(object):
         unfused path.  A model built with TRAIN_LOSS = "si-sdr" (`train_loss`) always takes the unfused heads and
         returns the waveform loss as `loss`, with its own permutation in `loss_perm_idx`.  A model built with
         DPCL_WEIGHT set (`dpcl_weight`) returns main loss + weight * deep-clustering loss as `loss` on every head
-        path, and the deep-clustering loss alone as `dpcl`.'''
+        path, and the deep-clustering loss alone as `dpcl`.  A model built with TRAIN_ESTIMATOR_METHOD = "truth-online"
+        gets a trajectory of attractors [B, T, C, E] from its estimator: it takes the unfused heads whatever fuse_heads
+        says, and `attrs` is the trajectory.'''
         B, E = hparams.BATCH_SIZE, hparams.EMBED_SIZE
         eps = float(hparams.EPS)
         if self._noise is None:
@@ -604,25 +610,30 @@ class Model(object):
             s_attractors = self.estimator(                     # main.py:251-254
                 s_embed, s_src_pwr=fe['src_pwr'], s_mix_pwr=fe['mix_pwr'])
             act = getattr(self.separator, 'ACT', None)
+            # "truth-online" returns per-frame attractors [B, T, C, E]: the unfused heads with ops.OnlineSeparateFn in
+            # the separator's place (the fused heads take one attractor set)
+            traj = s_attractors.dim() == 4
             if self.dpcl_weight is not None:
                 ops.unshare_dembed(s_attractors)       # the embedding gets a third consumer below
             if self.train_loss == 'si-sdr':
                 # the waveform loss needs the separated magnitudes: the unfused heads.  SNR, perm_idx and perms keep
                 # their meaning (one more launch, outside autograd); the loss's own permutation is loss_perm_idx
-                s_sep_pwr = self.separator(fe['mix_pwr'], s_attractors, s_embed_flat)
+                s_sep_pwr = (ops.OnlineSeparateFn.apply(fe['mix_pwr'], s_attractors, s_embed_flat, act) if traj else
+                             self.separator(fe['mix_pwr'], s_attractors, s_embed_flat))
                 loss, loss_idx = ops.si_sdr_loss(s_src_signals, s_sep_pwr, phasor)
                 with torch.no_grad():
                     _mse, perms, idx, snr = ops.pit_mse_loss(
                         s_src_signals, s_sep_pwr.detach(), phasor, mode=0, eps=eps)
                 out.update(attrs=s_attractors, sep_pwr=s_sep_pwr, loss=loss, SNR=snr,
                            perm_idx=idx, perms=perms, loss_perm_idx=loss_idx)
-            elif fuse_heads and act is not None and not hparams.DEBUG and not with_valid:
+            elif fuse_heads and act is not None and not hparams.DEBUG and not with_valid and not traj:
                 loss, perms, idx, snr = ops.separate_pit_loss(      # :271-272 + :281-290, 308-309
                     fe['mix_pwr'], s_attractors, s_embed_flat, s_src_signals, phasor, act,
                     mode=0, eps=eps)
                 out.update(attrs=s_attractors, loss=loss, SNR=snr, perm_idx=idx, perms=perms)
             else:
-                s_sep_pwr = self.separator(fe['mix_pwr'], s_attractors, s_embed_flat)  # :271-272
+                s_sep_pwr = (ops.OnlineSeparateFn.apply(fe['mix_pwr'], s_attractors, s_embed_flat, act) if traj else
+                             self.separator(fe['mix_pwr'], s_attractors, s_embed_flat))  # :271-272
                 loss, perms, idx, snr = ops.pit_mse_loss(          # main.py:289-290, 308-309
                     s_src_signals, s_sep_pwr, phasor, mode=0, eps=eps)
                 out.update(attrs=s_attractors, sep_pwr=s_sep_pwr, loss=loss, SNR=snr,

@@ -406,6 +406,27 @@ class OnlineEstimator(Estimator):
         return s_traj                                        # [B, T, C, E]
 
 
+@hparams.register_estimator('truth-online')
+class TruthOnlineEstimator(Estimator):
+    '''the training twin of `online` (include/danet_tonline_hip.h): per-frame attractors that are the running,
+    forgetting-weighted, |mix|-weighted means of the embedding under the IDEAL assignment of the frames seen so far, as
+    the Online Deep Attractor Network is trained.  NOT in the reference.  Hold length and forgetting factor are those of
+    the inference estimator (`model.online`: ONLINE_INIT_FRAMES, ONLINE_MEMORY_FRAMES), so it needs
+    INFER_ESTIMATOR_METHOD = "online".  Always returns the trajectory [B, T, C, E], also for T <= T0; has an exact
+    backward to the embedding and no parameters (the `anchors` of the hold's A0 are trained under "anchor" only).'''
+    USE_TRUTH = True
+
+    def __init__(self, model, name):
+        super(TruthOnlineEstimator, self).__init__(model, name)
+
+    def __call__(self, s_embed, s_src_pwr, s_mix_pwr, s_embed_flat=None):
+        T0, lam = self.model.online
+        s_traj = ops.TruthOnlineAttractorFn.apply(s_embed, s_src_pwr, s_mix_pwr, lam, T0, float(hparams.EPS))
+        if hparams.DEBUG:
+            self.debug_fetches = dict()
+        return s_traj                                        # float[B, T, C, E]
+
+
 class _DotSeparatorBase(Separator):
     ACT = None
 

@@ -1212,6 +1212,143 @@ def online_attractors(embed, w, a0, act, lam, T0, eps):
     return online_scan(embed.contiguous(), w.contiguous(), online_init(a0), act, lam, T0, eps)
 
 
+# ---- the truth-online estimator and the trajectory separator's backward (include/danet_tonline_hip.h) -----------
+# On the extension library libdanet_tonline_hip.so, mapped at the first call: only the train branch of a model built
+# with TRAIN_ESTIMATOR_METHOD = "truth-online" gets here.  Forward: frame_sums -> scan (-> online_separate); backward:
+# separate_bwd, scan_bwd -> sums_bwd.  Five launches beside the one of danet_online_separate.
+_tonline_ws = {}         # (device index, stream, B, T, C, E) -> (scratch, {s, q, r}): a cache of _scratch
+
+
+def _tonline_scratch(B, T, C, E, dev):
+    '''the intermediates that live between two launches: the frame sums s, q of the forward and R of the backward'''
+    return _scratch('tonline', _tonline_ws, (B, T, C, E),
+                    lambda: [('s', (B, T, C, E), torch.float32), ('q', (B, T, C), torch.float32),
+                             ('r', (B, T, C, E), torch.float32)], None, dev)[1]
+
+
+def tonline_frame_sums(embed, src_pwr, w, out=None):
+    '''danet_tonline_frame_sums, ONE launch: embed float32 [B, T, F, E], src_pwr float32 [B, C, T, F], w float32
+    [B, T, F] -> (s float32 [B, T, C, E], q float32 [B, T, C]), the W-weighted sums of every frame under the ideal
+    assignment'''
+    B, T, F, E = _chk('embed', embed, torch.float32, dim=4).shape
+    C = _chk('src_pwr', src_pwr, torch.float32, dim=4, dev=embed.device).shape[1]
+    _chk('src_pwr', src_pwr, torch.float32, (B, C, T, F))
+    _chk('w', w, torch.float32, (B, T, F), dev=embed.device)
+    out = out or (None, None)
+    s = _out('s', out[0], (B, T, C, E), torch.float32, embed.device)
+    q = _out('q', out[1], (B, T, C), torch.float32, embed.device)
+    with _lib.timed('tonline_frame_sums'):
+        _lib.tonline_check(_lib.load_tonline().danet_tonline_frame_sums(
+            _lib.stream(), B, C, T, F, E, ptr(embed), ptr(src_pwr), ptr(w), ptr(s), ptr(q)))
+    return s, q
+
+
+def tonline_scan(s, q, lam, T0, eps, out=None):
+    '''danet_tonline_scan, ONE launch: the frame sums s [B, T, C, E], q [B, T, C] -> (attr float32 [B, T, C, E], den
+    float64 [B, T, C]): the trajectory and the denominators n + eps the backward divides by'''
+    B, T, C, E = _chk('s', s, torch.float32, dim=4).shape
+    _chk('q', q, torch.float32, (B, T, C), dev=s.device)
+    out = out or (None, None)
+    attr = _out('attr', out[0], (B, T, C, E), torch.float32, s.device)
+    den = _out('den', out[1], (B, T, C), torch.float64, s.device)
+    with _lib.timed('tonline_scan'):
+        _lib.tonline_check(_lib.load_tonline().danet_tonline_scan(
+            _lib.stream(), B, C, T, E, float(lam), int(T0), float(eps), ptr(s), ptr(q), ptr(attr), ptr(den)))
+    return attr, den
+
+
+def tonline_scan_bwd(dattr, den, lam, T0, out=None):
+    '''danet_tonline_scan_bwd, ONE launch: dattr float32 [B, T, C, E] and the saved den float64 [B, T, C] -> r float32
+    [B, T, C, E], the gradient with respect to the frame sums of every frame'''
+    B, T, C, E = _chk('dattr', dattr, torch.float32, dim=4).shape
+    _chk('den', den, torch.float64, (B, T, C), dev=dattr.device)
+    r = _out('r', out, (B, T, C, E), torch.float32, dattr.device)
+    with _lib.timed('tonline_scan_bwd'):
+        _lib.tonline_check(_lib.load_tonline().danet_tonline_scan_bwd(
+            _lib.stream(), B, C, T, E, float(lam), int(T0), ptr(dattr), ptr(den), ptr(r)))
+    return r
+
+
+def tonline_sums_bwd(src_pwr, w, r, out=None):
+    '''danet_tonline_sums_bwd, ONE launch: dembed[b][t][f] = w[b][t][f] * r[b][t][label of the bin] -> float32
+    [B, T, F, E]'''
+    B, C, T, F = _chk('src_pwr', src_pwr, torch.float32, dim=4).shape
+    _chk('w', w, torch.float32, (B, T, F), dev=src_pwr.device)
+    E = _chk('r', r, torch.float32, dim=4, dev=src_pwr.device).shape[3]
+    _chk('r', r, torch.float32, (B, T, C, E))
+    dembed = _out('dembed', out, (B, T, F, E), torch.float32, src_pwr.device)
+    with _lib.timed('tonline_sums_bwd'):
+        _lib.tonline_check(_lib.load_tonline().danet_tonline_sums_bwd(
+            _lib.stream(), B, C, T, F, E, ptr(src_pwr), ptr(w), ptr(r), ptr(dembed)))
+    return dembed
+
+
+def tonline_separate_bwd(w, attr, embed, dout, act, out=None):
+    '''danet_tonline_separate_bwd, ONE launch: the backward of online_separate.  w [B, T, F], attr [B, T, C, E], embed
+    [B, T, F, E], dout [B, C, T, F], all float32 -> (dembed float32 [B, T, F, E], dattr float32 [B, T, C, E])'''
+    B, T, F, E = _chk('embed', embed, torch.float32, dim=4).shape
+    dev = embed.device
+    C = _chk('attr', attr, torch.float32, dim=4, dev=dev).shape[2]
+    _chk('attr', attr, torch.float32, (B, T, C, E))
+    _chk('w', w, torch.float32, (B, T, F), dev=dev)
+    _chk('dout', dout, torch.float32, (B, C, T, F), dev=dev)
+    out = out or (None, None)
+    dembed = _out('dembed', out[0], (B, T, F, E), torch.float32, dev)
+    dattr = _out('dattr', out[1], (B, T, C, E), torch.float32, dev)
+    with _lib.timed('tonline_separate_bwd'):
+        _lib.tonline_check(_lib.load_tonline().danet_tonline_separate_bwd(
+            _lib.stream(), int(act), B, C, T, F, E, ptr(w), ptr(attr), ptr(embed), ptr(dout), ptr(dembed), ptr(dattr)))
+    return dembed, dattr
+
+
+class TruthOnlineAttractorFn(torch.autograd.Function):
+    '''THE RULE of include/danet_tonline_hip.h: (embed [B, T, F, E], src_pwr [B, C, T, F], mix_pwr [B, T, F]) -> the
+    trajectory attr [B, T, C, E] of the running, forgetting-weighted means under the ideal assignment.  The gradient
+    goes to embed alone and is returned as an ordinary tensor: autograd adds it to the separator's.'''
+
+    @staticmethod
+    def forward(ctx, embed, src_pwr, mix_pwr, lam, T0, eps):
+        embed, src_pwr, mix_pwr = _f32(embed.contiguous()), _f32(src_pwr.contiguous()), _f32(mix_pwr.contiguous())
+        B, T, F, E = embed.shape
+        ws = _tonline_scratch(B, T, src_pwr.shape[1], E, embed.device)
+        s, q = tonline_frame_sums(embed, src_pwr, mix_pwr, out=(ws['s'], ws['q']))
+        attr, den = tonline_scan(s, q, lam, T0, eps)
+        ctx.save_for_backward(src_pwr, mix_pwr, den)
+        ctx.args = (lam, T0)
+        return attr
+
+    @staticmethod
+    def backward(ctx, dattr):
+        src_pwr, mix_pwr, den = ctx.saved_tensors
+        lam, T0 = ctx.args
+        B, T, C = den.shape
+        dattr = _f32(dattr.contiguous())
+        r = tonline_scan_bwd(dattr, den, lam, T0, out=_tonline_scratch(B, T, C, dattr.shape[3], dattr.device)['r'])
+        return tonline_sums_bwd(src_pwr, mix_pwr, r), None, None, None, None, None
+
+
+class OnlineSeparateFn(torch.autograd.Function):
+    '''online_separate with a backward: (mix_pwr [B, T, F], attr [B, T, C, E], embed_flat [B, T F, E] or [B, T, F, E],
+    act) -> sep [B, C, T, F].  Both gradients are returned as ordinary tensors.'''
+
+    @staticmethod
+    def forward(ctx, mix_pwr, attr, embed_flat, act):
+        mix_pwr, attr = _f32(mix_pwr.contiguous()), _f32(attr.contiguous())
+        B, T, F = mix_pwr.shape
+        embed = _f32(embed_flat.contiguous()).view(B, T, F, attr.shape[3])
+        out = online_separate(mix_pwr, attr, embed, act)
+        ctx.save_for_backward(mix_pwr, attr, embed)
+        ctx.args = (int(act), embed_flat.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        mix_pwr, attr, embed = ctx.saved_tensors
+        act, shape = ctx.args
+        dembed, dattr = tonline_separate_bwd(mix_pwr, attr, embed, _f32(dout.contiguous()), act)
+        return None, dattr, dembed.view(shape), None
+
+
 # ---- the causal encoder and block-wise streaming (include/danet_causal_hip.h) -----------------------------------
 # On the extension library libdanet_causal_hip.so, mapped at the first call: a run with another encoder and no stream
 # session never gets here.
